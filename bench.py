@@ -14,6 +14,11 @@ token visits the ranks that own its experts through ONE all-to-all out and ONE b
 scaling; value = all ranks' tokens / max-over-ranks time.  The whole expert-parallel step is captured in a
 hipGraph like the single-GPU step.
 
+A plain run (`--gpus N --steps K --warmup W`) does what the headline figure needs and no more: it sets up, warms up, times
+the K steps, writes the arrays of the last timed step if `--dump-outputs DIR` is given, and prints the headline line with
+`roofline` and `cpu_baseline` null.  Whatever below takes runs of its own -- `roofline`, `long_run`, `cpu_baseline`, the extra
+workloads, the `--full-out` side file -- is behind `--full`.
+
 Output (rank 0, stdout).  The LAST line is the headline object and nothing else (contract in the task statement:
 metric, value, ms_per_step, steps, dtype, config.workload, `roofline` of the dominant kernel = GEMM1 -- algorithmic
 weight bytes / the median of its HIP-event durations on the launch stream, kernel name taken from the launch --
@@ -113,6 +118,8 @@ EXTRA_N1 = [# the headline workload under Zipf routing first, in the thermal sta
 EXTRA_EP = "dsv3_fp8w8a8_ep_decode_b256"
 HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 MFMA_PEAK_TF = {"bf16": 2500.0, "fp8": 5000.0}   # dense, MI355X_MICROARCH.md
+DUMP_BYTES = 48 << 20       # --dump-outputs: the arrays of all ranks together stay below this
+REGIONS_BUDGET_S = 1.0      # the timed region is repeated (--regions) only where all repeats together stay below this
 
 
 # ------------------------------------------------------------------------------------------ synthetic weights
@@ -443,9 +450,30 @@ def roof_fields(flops, bytes_, ms, peak_tf):
             "roof_bound": "mfma" if roof_tf >= peak_tf else "hbm", "frac_of_roof": round(tf / roof_tf, 4)}
 
 
-def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, routing=None):
+def dump_outputs(dirname, arrays, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, one float32 DIR/<name>.npy per array (a rank of a
+    multi-GPU run adds _rank<r> to the name).  Where that would pass DUMP_BYTES over all ranks, the same seeded sample of
+    rows of every array is kept and its row numbers go to sampled_rows.npy."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    rows = next(iter(arrays.values())).size(0)
+    row_bytes = sum(t[0].numel() for t in arrays.values()) * 4
+    keep = None
+    if rows * row_bytes > DUMP_BYTES // world:
+        keep = np.sort(np.random.default_rng(0).choice(rows, DUMP_BYTES // world // row_bytes, replace=False))
+        np.save(d / f"sampled_rows{tag}.npy", keep.astype(np.float64))
+    for k_, t in arrays.items():
+        if keep is not None:
+            t = t[torch.from_numpy(keep).to(t.device)]
+        np.save(d / f"{k_}{tag}.npy", t.float().cpu().numpy())
+
+
+def run_workload(name, args, ctx, *, steps, warmup, with_cpu, full, force_ep=False, routing=None, dump_dir=None):
     """times `steps` steps of one WORKLOADS entry on this rank set; returns the result dict on rank 0 (None
-    elsewhere).  Every rank must call it with the same arguments (it contains collectives when world > 1)."""
+    elsewhere).  Every rank must call it with the same arguments (it contains collectives when world > 1).
+    full (bench.py --full): also the longer run of the same step, the per-kernel roofline pass and, with_cpu, the CPU
+    baselines -- runs of their own after the timed steps, which a plain run leaves out (`roofline`: null)."""
     from lvllm_amd import ops
     from lvllm_amd.ep import ExpertParallelExperts
     world, rank, dev = ctx["world"], ctx["rank"], ctx["dev"]
@@ -502,11 +530,12 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
     prefill = bool(wl.get("prefill"))
     out = torch.empty((M, H), dtype=torch.bfloat16 if prefill else torch.float32, device=dev)
     ep = None
+    last = {}       # what the latest step() handed back (a captured step: the graph's own tensors, rewritten by every replay)
     if not use_ep:
         if prefill:
             def step():
                 tw, ids = route()
-                eng.forward_rows(x, tw, ids, out=out)
+                last["ret"] = (eng.forward_rows(x, tw, ids, out=out), tw, ids)
         else:
             # decode: routing + scatter metadata in one launch (lkm_forward_routed; --tune fuse=-1 gives the five-launch
             # step back; same bits)
@@ -516,7 +545,7 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
                           routed_scaling_factor=rt["routed_scaling"])
 
             def step():
-                eng.forward_logits(x, logits, K, True, **fl)
+                last["ret"] = eng.forward_logits(x, logits, K, True, **fl)
     else:
         def local_compute(rows, lids, ws, dt, valid_den=None):
             # (a2a mode hands over ep x capacity token records of which ~1/ep carry local ids and says so: valid_den)
@@ -530,7 +559,7 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
 
         def step():
             tw, ids = route()
-            ep.forward(x, tw, ids, force_collectives=True, out=out)
+            last["ret"] = (ep.forward(x, tw, ids, force_collectives=True, out=out), tw, ids)
 
     def barrier():
         if ctx["dist"]:
@@ -620,9 +649,14 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
     # R = 5 regions back to back and the MEDIAN region is the line's value (all five are reported, `timed_regions_ms`):
     # the pool's boxes freeze the GPU queue for ~86 ms now and then (tools/prof_rep_stall.py, profiles/r05_prof_rep_stall.log:
     # twice in ~2 s of launches on one box -- the event that turned round 4's driver test run red); one such event inside a
-    # 9 ms region of 20 steps would report a tenth of the throughput.  --regions 1 gives the single region back.
+    # 9 ms region of 20 steps would report a tenth of the throughput.  --regions 1 gives the single region back.  The
+    # repeats are there for SHORT regions: when R times the first region would pass REGIONS_BUDGET_S the first one stands
+    # alone (its reduced time is the same on every rank, so the ranks decide alike), and a run whose --steps fill a second
+    # times exactly those steps, once.
     regions = []
     for _ in range(max(1, args.regions)):
+        if regions and regions[0] * args.regions > REGIONS_BUDGET_S:
+            break
         barrier()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -637,6 +671,8 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
     tokens_per_s = M * world / (dt / steps)
     if wd is not None:
         wd.disarm()
+    if dump_dir:
+        dump_outputs(dump_dir, dict(zip(("out", "topk_weights", "topk_ids"), last["ret"])), rank, world)
 
     # ---- the same step over a longer run (reported next to the line's value, never instead of it): right after the
     # synchronisation that opens a timed region the GPU clocks ramp for a few milliseconds, which a 20-step region of a
@@ -644,7 +680,7 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
     # profiles/r03_timed_region_length.log)
     long_run = None
     LONG = 400
-    if steps < LONG and not prefill_like(wl) and not use_ep:
+    if full and steps < LONG and not prefill_like(wl) and not use_ep:
         barrier()
         t0 = time.perf_counter()
         for _ in range(LONG):
@@ -672,11 +708,13 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
 
     # ---- dominant-kernel roofline: GEMM1 duration from HIP events on the launch stream (rank 0's engine)
     res = None
-    tw, ids = route()
-    lids = ids
-    if world > 1:
-        lids = torch.where((ids >= first) & (ids < first + E_local), ids - first, torch.full_like(ids, -1))
-    if rank == 0:
+    if full:
+        tw, ids = route()
+        lids = ids
+        if world > 1:
+            lids = torch.where((ids >= first) & (ids < first + E_local), ids - first, torch.full_like(ids, -1))
+
+    def measure_roofline():
         # each GEMM is launched PROF_REP times back to back between its two events and the interval divided
         # (lkm_set_tuning "prof_rep"): a single launch between two events also times the event packets,
         # ~10 us on top of the kernel time rocprofv3 reports for the same launch
@@ -770,6 +808,9 @@ def run_workload(name, args, ctx, *, steps, warmup, with_cpu, force_ep=False, ro
             "kernel_ms_min_max": prof_range, "gemm2_kernel": "+".join(kernels.get("gemm2", [])) or None, "plan": plan,
             "timing": f"HIP events on the launch stream around {PROF_REP} back-to-back launches, / {PROF_REP}; median of {reps} calls"
                       + (" (rank 0's engine on rank 0's own routed rows)" if world > 1 else "")})
+        return roofline
+    if rank == 0:
+        roofline = measure_roofline() if full else None
         res = {"workload": name, "value": round(tokens_per_s, 1), "unit": "tokens/s", "ms_per_step": round(ms_per_step, 4),
                "steps": steps, "scaling": scaling, "timed_regions_ms": [round(r * 1e3, 3) for r in regions],
                "dtype": {"bf16": "bf16", "int4": "int4-w/bf16-act" + {0: "", 1: " (fast mode: scale on fp32 partial sums)", 2: " (zero points: T((q - zp) s))"}[int(wl.get("int4_mode", 0))],
@@ -882,8 +923,15 @@ def main():
                     help="dtype of the partial rows on the return all-to-all (bf16 = the activation dtype)")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
     ap.add_argument("--force-ep", action="store_true", help="run the expert-parallel data path even with one rank (plumbing check)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="time the headline workload only")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also: the per-kernel roofline pass, a longer run of the same step, the CPU "
+                         "baselines, the extra workloads and the --full-out side file (a plain run times the steps and prints "
+                         "the line, with `roofline` and `cpu_baseline` null)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (out, topk_weights, topk_ids) as float32 DIR/<name>.npy; the "
+                         "inputs are seeded, so two builds run with the same arguments can be compared array by array")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baselines out")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: time the headline workload only")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="budget (s) for each CPU baseline sample (reference kernel, port)")
     ap.add_argument("--routing", default="uniform", choices=["uniform", "zipf", "biased", "nobias"],
                     help="router logits: randn (uniform-ish; the sigmoid + bias routers run a ZERO score-correction bias) or "
@@ -894,7 +942,8 @@ def main():
     ap.add_argument("--no-autotune", action="store_true", help="(default since round 5; kept so that older command lines still parse)")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="override the workload's tokens per GPU (plan A/Bs; not for the headline)")
     ap.add_argument("--regions", type=int, default=5,
-                    help="timed regions of exactly --steps steps each; the median region is reported (all are listed)")
+                    help="timed regions of exactly --steps steps each; the median region is reported (all are listed); "
+                         "regions of more than 1/REGIONS of a second are timed once")
     ap.add_argument("--full-line", action="store_true", help="print the complete record as the last line (tools), not the < 4 KB one")
     ap.add_argument("--full-out", default=str(ROOT / "gpurun_out" / "bench_full.json"),
                     help="side file for the complete records of the headline and the extra workloads ('' = none)")
@@ -924,7 +973,8 @@ def main():
     ctx = dict(world=world, rank=rank, dev=dev, dist=use_dist, wd=Watchdog(rank) if (world > 1 or (use_dist and os.environ.get("LKM_BENCH_WATCHDOG") == "1")) else None)
 
     head = run_workload(args.workload, args, ctx, steps=args.steps, warmup=args.warmup,
-                        with_cpu=not args.no_cpu_baseline, force_ep=args.force_ep)
+                        with_cpu=args.full and not args.no_cpu_baseline, full=args.full, force_ep=args.force_ep,
+                        dump_dir=args.dump_outputs)
     def make_line(head, extras=None):
         """the headline object: the contract's fields + a roofline / cpu_baseline cut to what the judge reads (< 4 KB)"""
         rf = head.get("roofline") or {}
@@ -976,10 +1026,11 @@ def main():
                 "plan": rf.get("plan"), "exchange": r["config"].get("exchange")}
 
     extras = []
-    if ctx["wd"] is not None and not args.no_extras and args.workload == HEADLINE:
+    with_extras = args.full and not args.no_extras and args.workload == HEADLINE
+    if ctx["wd"] is not None and with_extras:
         # (rank 0 holds the finished headline line from here on; the other ranks only need a non-None marker)
         ctx["wd"].arm(600.0, make_line(head) if head is not None else ({} if rank else None), "the extra workloads")
-    if not args.no_extras and args.workload == HEADLINE:
+    if with_extras:
         es, ew = min(args.steps, 100), min(args.warmup, 10)
         names = (EXTRA_N1 if world == 1 and not args.force_ep else []) + [EXTRA_EP]
         for n in names:
@@ -989,7 +1040,7 @@ def main():
             else:
                 es_n, ew_n = es, ew
             try:
-                r = run_workload(n, args, ctx, steps=es_n, warmup=ew_n, with_cpu=False,
+                r = run_workload(n, args, ctx, steps=es_n, warmup=ew_n, with_cpu=False, full=True,
                                  force_ep=args.force_ep and n == EXTRA_EP, routing=rt_over)
             except Exception as e:   # an extra must never take the headline line with it
                 if use_dist:
@@ -1005,7 +1056,7 @@ def main():
     if rank == 0:
         if head is None:
             sys.exit(f"workload {args.workload} does not shard over {world} GPUs")
-        if args.full_out:
+        if args.full and args.full_out:
             try:
                 fp = Path(args.full_out)
                 fp.parent.mkdir(parents=True, exist_ok=True)

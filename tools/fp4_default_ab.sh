@@ -1,5 +1,5 @@
 for rep in 1 2; do for wl in mixtral8x7b_mxfp4_decode_m128 mixtral8x7b_nvfp4_decode_m128; do for r in uniform zipf; do for t in "" "pf=6,tiled=64" "pf=5,tiled=64"; do
-  out=$(python bench.py --workload $wl --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $r ${t:+--tune $t} 2>/dev/null | tail -1)
+  out=$(python bench.py --workload $wl --full --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $r ${t:+--tune $t} 2>/dev/null | tail -1)
   echo "$out" | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); r=j['roofline']; km=r['kernel_ms']

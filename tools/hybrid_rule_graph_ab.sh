@@ -2,7 +2,7 @@
 # The round-5 plan rules (tiles instead of the hybrid) through bench.py's CAPTURED step, same box: default against "hybrid" = 1
 # (the round-4 plan).   bash tools/hybrid_rule_graph_ab.sh   (GPU box)
 one() {  # workload M routing tune
-  out=$(python bench.py --workload $1 --batch-per-gpu $2 --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $3 ${4:+--tune $4} 2>/dev/null | tail -1)
+  out=$(python bench.py --workload $1 --batch-per-gpu $2 --full --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $3 ${4:+--tune $4} 2>/dev/null | tail -1)
   echo "$out" | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); r=j['roofline']; km=r['kernel_ms']

@@ -3,7 +3,7 @@
 # round-5 default (GEMM1 tile kernel + GEMM2 gemm_w4e.h), gemm_w4e.h for both ("pf" = 6) and gemm_w4x.h ("pf" = 5), uniform and
 # Zipf.   bash tools/int4_default_ab.sh   (GPU box)
 for rep in 1 2; do for r in uniform zipf; do for t in "pf=-1" "" "pf=6,tiled=64" "pf=5,tiled=64"; do
-  out=$(python bench.py --workload mixtral8x7b_int4g128_decode_m128 --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $r ${t:+--tune $t} 2>/dev/null | tail -1)
+  out=$(python bench.py --workload mixtral8x7b_int4g128_decode_m128 --full --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $r ${t:+--tune $t} 2>/dev/null | tail -1)
   echo "$out" | python -c "
 import json,sys
 j=json.loads(sys.stdin.read()); r=j['roofline']; km=r['kernel_ms']

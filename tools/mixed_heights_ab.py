@@ -13,7 +13,7 @@ SETTINGS = ["mixed=-1", "mixed=0", "mixed=48", "mixed=96", "mixed=-1,tiled=64", 
 
 
 def run(wl, routing, tune):
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--steps", STEPS, "--warmup", "5", "--no-cpu-baseline",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--steps", STEPS, "--warmup", "5", "--full", "--no-cpu-baseline",
            "--no-extras", "--full-line", "--full-out", "", "--routing", routing, "--tune", tune]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     line = next((l for l in reversed(r.stdout.splitlines()) if l.startswith("{")), None)

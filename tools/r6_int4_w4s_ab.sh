@@ -6,7 +6,7 @@ reps=${1:-2}
 for rep in $(seq 1 $reps); do for r in uniform zipf; do
   for t in "" "pf=7,tiled=64,pd1=6,pd2=6" "pf=7,tiled=64,pd1=3,pd2=3" "pf=7,tiled=64,pd1=4,pd2=4" "pf=7,tiled=64,pd1=8,pd2=8" \
            "pf=7,tiled=64,pd1=6,pd2=6,waves=8" "pf=7,tiled=64,pd1=4,pd2=4,waves=8" "pf=7,tiled=64,pd1=6,pd2=6,sk2=1" "pf=7,tiled=64,pd1=8,pd2=8,sk2=2"; do
-  out=$(python bench.py --workload mixtral8x7b_int4g128_decode_m128 --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $r ${t:+--tune $t} 2>/dev/null | tail -1)
+  out=$(python bench.py --workload mixtral8x7b_int4g128_decode_m128 --full --no-extras --no-cpu-baseline --full-out "" --steps 200 --routing $r ${t:+--tune $t} 2>/dev/null | tail -1)
   echo "$out" | python -c "
 import json,sys
 try:

@@ -35,7 +35,7 @@ RUNS = [
 
 def run(workload, steps, routing):
     cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", workload, "--steps", str(steps), "--warmup",
-           "5", "--no-cpu-baseline", "--no-extras", "--full-line", "--routing", routing]
+           "5", "--full", "--no-cpu-baseline", "--no-extras", "--full-line", "--routing", routing]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     for line in r.stdout.splitlines():
         if line.startswith("{"):

@@ -49,7 +49,7 @@ def main():
         # engine defaults (no autotune: a tuning pass would launch candidate kernels of other plans), eager launches
         cmd = ["rocprofv3", "--kernel-trace", "--pmc", "FETCH_SIZE", "-d", str(d), "-o", "p", "--", sys.executable,
                str(ROOT / "bench.py"), "--workload", wl, "--routing", routing, "--no-cpu-baseline", "--no-extras", "--no-graph",
-               "--full-line", "--full-out", "", "--steps", "10", "--warmup", "3"]
+               "--full", "--full-line", "--full-out", "", "--steps", "10", "--warmup", "3"]
         r = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=900)
         line = next((l for l in reversed(r.stdout.splitlines()) if l.startswith("{")), None)
         s = subprocess.run([sys.executable, str(ROOT / "tools" / "rocprof_summary.py"), str(d / "p_results.db"), "--pmc"],
