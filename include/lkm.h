@@ -30,7 +30,7 @@ extern "C" {
 #define LKM_E_INVALID (-1)     /* bad argument / unsupported configuration */
 #define LKM_E_HIP (-2)         /* HIP runtime error (message has the hipError string) */
 #define LKM_E_NOMEM (-3)
-#define LKM_E_UNSUPPORTED (-4) /* format known but not built yet (NVFP4 / MXFP4) */
+#define LKM_E_UNSUPPORTED (-4) /* no kernel built for this (weight format, activation dtype) pair */
 
 /* activation (hidden-state) dtypes: suffix of the lk_moe class name
  * (MOE_BF16 vs MOE_FP16 ..., routed_experts.py:1514-1533) */
@@ -46,6 +46,10 @@ extern "C" {
 #define LKM_W_NVFP4 4    /* MOE_NVFP4[_FP16]  : E2M1 bytes [E,N,K/2] + fp8 e4m3fn block scales       *
                           *   [E,N,K/16] (linear) + per-expert f32 multipliers [E] (global)  */
 #define LKM_W_MXFP4 5    /* MOE_MXFP4[_FP16]  : E2M1 bytes [E,N,K/2] + uint8 E8M0 scales [E,N,K/32]  */
+#define LKM_W_INT8 6     /* weight-only 8 bits (the in-tree operator's int8_w8a16, fused_moe.py:207-276; no lk_moe class): *
+                          *   uint8 bytes [E,N,K] + act-dtype scales [E,N,K/group] (groupN == 1, the group rule of         *
+                          *   LKM_W_INT4_B8), dequantised to T((q - zp) * s).  Zero points: uint8 [E,N,K/group] in the two  *
+                          *   global-scale pointer slots; both NULL = symmetric uint8b128 (zp = 128)                        */
 
 /* MOEConfigV2.activation_type (routed_experts.py:160-164) */
 #define LKM_ACT_SILU 0
@@ -117,7 +121,8 @@ typedef struct LkmEngine* LkmHandle;
  * memory (detected); contiguous, layouts of SURVEY 8(a5).  The engine COPIES the weights
  * (pre-shuffled into its MFMA-native HBM layout) -- the caller frees its tensors right
  * after (routed_experts.py:1420-1432).  NULL = absent.  The two global-scale slots carry the NVFP4 per-expert multipliers
- * (fp32 [E]) or, with weight_format LKM_W_INT4_B8 and int4_mode LKM_INT4_ZP, the zero points (uint8 [E, rows, K / group]).
+ * (fp32 [E]) or, with weight_format LKM_W_INT4_B8 and int4_mode LKM_INT4_ZP, or with LKM_W_INT8 (optional there: both or neither),
+ * the zero points (uint8 [E, rows, K / group]).
  */
 int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2, const void* w13_scale,
                const void* w2_scale, const void* w13_global_scale, const void* w2_global_scale,

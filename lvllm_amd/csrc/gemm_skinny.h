@@ -205,6 +205,68 @@ struct Dec<LKM_W_INT4_ZP, ADT> {
     }
 };
 
+// weight-only uint8 (LKM_W_INT8, lkm_common.h): one byte per weight in the fp8 image (a lane's 8 bytes of k-step ks are the two
+// dwords (ks & 1) * 2, + 1 of load ks >> 1), the (scale, zero point) pairs of the zero-point decoder above -- same 16-byte
+// fetch, same pair selection; a symmetric uint8b128 layer carries zero point 128 in every pair and runs the same code.
+//   w = RNE_T(fma(float(q), s, -zp * s))
+// is the reference's T((q - zp) * s) (fused_moe.py:272-276) bit for bit: q and zp are integers <= 255 (8 bits) and s, a bf16 /
+// fp16 number, has <= 11 significant bits, so zp * s (<= 19 bits) is an exact fp32 product, and the fma's exact value
+// (q - zp) * s (|q - zp| <= 255: <= 19 bits, <= 20 with the issue's slack) is representable in fp32 as well -- the fma does not
+// round, the pack to the activation dtype is the only rounding.
+// VALU per 16 x 32 fragment (8 weights per lane), counted in the gfx950 ISA of the streamer's steady loop (gemm2_kernel<NT 1,
+// TB 1>, bf16: two units = 8 fragments): 8 v_cvt_f32_ubyteN + 4 v_pk_fma_f32 + 4 v_cvt_pk_bf16_f32 = 16, plus 5.6 for the
+// multipliers of the fragment's (row, group) (1.5 v_cndmask pair select, v_and + v_lshlrev to fp32, v_mov + v_pk_mul for the two
+// {v, v} pairs) -- formed per k-step whatever the group, the pair index (ks * spu) >> 2 is a run-time value; 207 VALU per 8 MFMA
+// in that loop with the addressing.  The fp8 decoder next to it takes 8.  No cheaper exact sequence found: a byte has no packed conversion
+// (v_cvt_pk_f32_fp8 is linear only on 0..15, the int4 trick), and the byte-into-mantissa form (2^23 + q) moves the conversion to
+// one v_perm_b32 per weight but needs a separate subtract before the multiply (the addend (2^23 + zp) * s is not an fp32 number).
+template <int ADT>
+struct Dec<LKM_W_INT8, ADT> {
+    static constexpr int UNITK = 128, LOADS = 2, KSTEPS = 4;
+    static constexpr bool UNIT_SCALE = false, A8 = false, XS = false;
+    typedef Dec<LKM_W_INT4_ZP, ADT> ZP;
+    typedef typename ZP::Aux Aux;      // up to four (scale, zero point) pairs of this lane's weight row for the 128-k unit
+    static __device__ __forceinline__ void load_aux(Aux& a, const void* sbase, size_t tu, int lane, int spu) { ZP::load_aux(a, sbase, tu, lane, spu); }
+    static __device__ __forceinline__ const char* aux_ptr(const void* sbase, size_t tu, int lane, int spu) { return ZP::aux_ptr(sbase, tu, lane, spu); }
+    static __device__ __forceinline__ int aux_step(int spu) { return ZP::aux_step(spu); }
+    static __device__ __forceinline__ void load_aux_at(Aux& a, const char* p) { ZP::load_aux_at(a, p); }
+    // the two multipliers of a (row, scale group): {s, s} and {-zp s, -zp s}
+    struct Mult {
+        f32x2 s, zs;
+    };
+    static __device__ __forceinline__ Mult mult(const Aux& a, int ks, int spu) {
+        const int idx = (ks * spu) >> 2;   // 0 for g>=128, ks/2 for g=64, ks for g=32 (wave-uniform)
+        const unsigned pair = idx == 0 ? a.raw.x : (idx == 1 ? a.raw.y : (idx == 2 ? a.raw.z : a.raw.w));
+        const float s = ActT<ADT>::to_f32((unsigned short)(pair & 0xffffu));
+        const float z = ActT<ADT>::to_f32((unsigned short)(pair >> 16));
+        // two full pairs behind empty asm statements, never one pair {s, -zp s} read through two op_sel swizzles: see
+        // splat2_opaque, lkm_common.h
+        Mult m;
+        m.s = f32x2{s, s};
+        asm("" : "+v"(m.s));
+        m.zs = m.s * f32x2{-z, -z};
+        asm("" : "+v"(m.zs));
+        return m;
+    }
+    static __device__ __forceinline__ u32x4 frag_m(const u32x4 (&raw)[LOADS], int ks, const Mult& m) {
+        const unsigned d0 = raw[ks >> 1][(ks & 1) * 2], d1 = raw[ks >> 1][(ks & 1) * 2 + 1];   // k = 0..3, 4..7 of the lane's 8
+        // (float)(byte N of a dword) is one v_cvt_f32_ubyteN
+        const f32x2 q01 = {(float)(d0 & 0xffu), (float)((d0 >> 8) & 0xffu)}, q23 = {(float)((d0 >> 16) & 0xffu), (float)(d0 >> 24)};
+        const f32x2 q45 = {(float)(d1 & 0xffu), (float)((d1 >> 8) & 0xffu)}, q67 = {(float)((d1 >> 16) & 0xffu), (float)(d1 >> 24)};
+        const f32x2 w01 = __builtin_elementwise_fma(q01, m.s, m.zs), w23 = __builtin_elementwise_fma(q23, m.s, m.zs);
+        const f32x2 w45 = __builtin_elementwise_fma(q45, m.s, m.zs), w67 = __builtin_elementwise_fma(q67, m.s, m.zs);
+        u32x4 o;
+        o.x = ActT<ADT>::pack2(w01.x, w01.y);
+        o.y = ActT<ADT>::pack2(w23.x, w23.y);
+        o.z = ActT<ADT>::pack2(w45.x, w45.y);
+        o.w = ActT<ADT>::pack2(w67.x, w67.y);
+        return o;
+    }
+    static __device__ __forceinline__ u32x4 frag(const u32x4 (&raw)[LOADS], const Aux& a, int ks, int spu) {
+        return frag_m(raw, ks, mult(a, ks, spu));
+    }
+};
+
 // uint4b8, fast mode (LKM_W_INT4_PS, lkm_common.h): 7 VALU per 16 x 32 fragment (three shifts, four v_and_or_b32)
 // where the bit-exact decoder above needs 16-19.  A nibble v in the low bits of the mantissa of BIAS = 2^7 (bf16)
 // / 2^10 (fp16) IS the value BIAS + v; the pair order of the re-packed dword (repack.hip) makes dword p of the

@@ -64,6 +64,8 @@ constexpr int tiled_min_blocks(int wf, int tbw, int waves, bool gated_g1, int pd
     if ((wf == LKM_W_INT4_B8 || wf == LKM_W_MXFP4 || wf == LKM_W_NVFP4) && tbw == 2 && waves == 4 && gated_g1 && pd == 2) return 4;
     // (the fp8 kernels sit 34 registers above that budget: forced there they spill 156-236 B and LOSE,
     // DSv3 rank slice GEMM1 151 -> 178 us)
+    // (uint8, LKM_W_INT8, holds twice the raw weight registers of a 4-bit format per stage: its non-gated 32-row kernels need
+    // 88 registers where uint4 + zero points needs 78 -- five waves per SIMD against six; asked for six, they spill 36 B: not forced)
     return 1;
 }
 
@@ -546,9 +548,13 @@ template <int WF>
 struct W4Only {
     static constexpr bool value = WF == LKM_W_INT4_B8 || WF == LKM_W_INT4_PS || WF == LKM_W_MXFP4 || WF == LKM_W_NVFP4;
 };
+// (uint8 on 128-row tiles: the four-stage weight ring does not fit the registers -- 256 B of scratch -- and is not built;
+//  "pd" = 4 runs the two-stage kernel there)
 #define LKM_TILED_CASE(TBW, WAVES, NT, G, IS1)                                             \
     if (cfg.tiled == TBW * 16 && cfg.waves == WAVES && cfg.nt == NT) {                                  \
-        if (cfg.pd >= 4) return launch_tiled_t<WF_, ADT_, NT, TBW, WAVES, G, IS1, 4>(st, p, max_tiles); \
+        if constexpr (!(WF_ == LKM_W_INT8 && TBW == 8)) {                                               \
+            if (cfg.pd >= 4) return launch_tiled_t<WF_, ADT_, NT, TBW, WAVES, G, IS1, 4>(st, p, max_tiles); \
+        }                                                                                               \
         return launch_tiled_t<WF_, ADT_, NT, TBW, WAVES, G, IS1, 2>(st, p, max_tiles);                 \
     }
 

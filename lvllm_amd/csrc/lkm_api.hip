@@ -274,7 +274,8 @@ static size_t wbytes_per_elem_x2(int wf) {  // bytes per 2 elements
     switch (wf) {
     case LKM_W_BF16:
     case LKM_W_F16: return 4;
-    case LKM_W_FP8_E4M3: return 2;
+    case LKM_W_FP8_E4M3:
+    case LKM_W_INT8: return 2;
     default: return 1;
     }
 }
@@ -336,7 +337,7 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
     *out = nullptr;
     LKM_REQUIRE(cfg->abi_version == LKM_ABI_VERSION, "lkm_create: ABI version %d != %d", cfg->abi_version, LKM_ABI_VERSION);
     const int wf = cfg->weight_format, adt = cfg->act_dtype;
-    LKM_REQUIRE(wf >= LKM_W_BF16 && wf <= LKM_W_MXFP4, "lkm_create: bad weight_format %d", wf);
+    LKM_REQUIRE(wf >= LKM_W_BF16 && wf <= LKM_W_INT8, "lkm_create: bad weight_format %d", wf);
     LKM_REQUIRE(adt == LKM_DT_BF16 || adt == LKM_DT_F16, "lkm_create: act_dtype must be bf16 or fp16");
     LKM_REQUIRE(!(wf == LKM_W_BF16 && adt != LKM_DT_BF16) && !(wf == LKM_W_F16 && adt != LKM_DT_F16),
                 "lkm_create: unquantised weights must have the activation dtype");
@@ -373,15 +374,20 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         LKM_REQUIRE(cfg->groupK == g && cfg->groupN == 1, "lkm_create: %s block scales are 1 x %d (got groupN=%d groupK=%d)", wf == LKM_W_MXFP4 ? "MXFP4" : "NVFP4", g, cfg->groupN, cfg->groupK);
         LKM_REQUIRE(cfg->hidden_size % 32 == 0 && cfg->intermediate_size % 32 == 0, "lkm_create: fp4 formats need hidden and intermediate sizes that are multiples of 32");
     }
-    if (wf == LKM_W_INT4_B8) {
-        LKM_REQUIRE(w13_scale && w2_scale, "lkm_create: int4 weights need scales");
-        LKM_REQUIRE(cfg->groupN == 1, "lkm_create: int4 expects groupN == 1 (got %d)", cfg->groupN);
+    if (wf == LKM_W_INT4_B8 || wf == LKM_W_INT8) {      // weight-only integers: one group rule
+        const char* nm = wf == LKM_W_INT8 ? "int8" : "int4";
+        LKM_REQUIRE(w13_scale && w2_scale, "lkm_create: %s weights need scales", nm);
+        LKM_REQUIRE(cfg->groupN == 1, "lkm_create: %s expects groupN == 1 (got %d)", nm, cfg->groupN);
         for (int which = 0; which < 2; ++which) {
             const int g = which ? gk2 : gk13, kk = which ? cfg->intermediate_size : cfg->hidden_size;
-            LKM_REQUIRE(g >= 32 && (g <= 128 ? 128 % g == 0 : g % 128 == 0), "lkm_create: int4 groupK=%d (group of GEMM%d: %d) unsupported (32, 64, 128 or a multiple of 128)", cfg->groupK, which + 1, g);
-            LKM_REQUIRE(kk % g == 0, "lkm_create: int4 group %d must divide K=%d of GEMM%d", g, kk, which + 1);
+            LKM_REQUIRE(g >= 32 && (g <= 128 ? 128 % g == 0 : g % 128 == 0), "lkm_create: %s groupK=%d (group of GEMM%d: %d) unsupported (32, 64, 128 or a multiple of 128)", nm, cfg->groupK, which + 1, g);
+            LKM_REQUIRE(kk % g == 0, "lkm_create: %s group %d must divide K=%d of GEMM%d", nm, g, kk, which + 1);
         }
-        LKM_REQUIRE((gk13 >= 128) == (gk2 >= 128) && (gk13 >= 128 || gk13 == gk2), "lkm_create: int4 groups of the two GEMMs (%d, %d) need the same scales per 128-k unit", gk13, gk2);
+        LKM_REQUIRE((gk13 >= 128) == (gk2 >= 128) && (gk13 >= 128 || gk13 == gk2), "lkm_create: %s groups of the two GEMMs (%d, %d) need the same scales per 128-k unit", nm, gk13, gk2);
+    }
+    if (wf == LKM_W_INT8)
+        LKM_REQUIRE((w13_gs == nullptr) == (w2_gs == nullptr), "lkm_create: int8 zero points (uint8 [E, rows, K / group], the two global-scale pointer slots) come for both GEMMs or for neither");
+    if (wf == LKM_W_INT4_B8) {
         const int g = gk13 < gk2 ? gk13 : gk2;
         LKM_REQUIRE(cfg->int4_mode == LKM_INT4_EXACT || cfg->int4_mode == LKM_INT4_FAST || cfg->int4_mode == LKM_INT4_ZP, "lkm_create: bad int4_mode %d", cfg->int4_mode);
         LKM_REQUIRE(cfg->int4_mode != LKM_INT4_ZP || (w13_gs && w2_gs), "lkm_create: int4_mode ZP takes the zero points (uint8 [E, rows, K / group]) in the two global-scale pointer slots");
@@ -419,7 +425,7 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
     h->T2 = round_up(ceil_div(h->H, 16), 4);
     h->U2 = ceil_div(h->I, h->unitk);
     h->ld_act = h->I;
-    h->spu = (wf == LKM_W_INT4_B8) ? (gk13 >= 128 ? 1 : 128 / gk13) : 0;
+    h->spu = (wf == LKM_W_INT4_B8 || wf == LKM_W_INT8) ? (gk13 >= 128 ? 1 : 128 / gk13) : 0;
 
     const int loads = wf_loads(wf);
     const int halves = gated ? 2 : 1;
@@ -493,15 +499,21 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         auto rs2 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4ps(nullptr, sp, dp, dd, gk2, adt); };
         LKM_TRY(hand_off(w13_scale, (size_t)halves * h->I * (h->H / gk13) * 2, h->s13, n13 * 4, d13, rs13));
         LKM_TRY(hand_off(w2_scale, (size_t)h->H * (h->I / gk2) * 2, h->s2, n2 * 4, d2, rs2));
-    } else if (h->zp) {     // (scale, zero point) pairs: two passes over one image, the zero points from the global-scale slots
+    } else if (h->zp || wf == LKM_W_INT8) {     // (scale, zero point) pairs: two passes over one image, the zero points from the global-scale slots
+        const int zmask = wf == LKM_W_INT8 ? 255 : 15;
         const size_t n13 = (size_t)halves * h->T1_half * h->U1 * 16 * h->spu, n2 = (size_t)h->T2 * h->U2 * 16 * h->spu;
         LKM_TRY_HIP(hipMalloc(&h->s13, h->E * n13 * 4 + 16));   // +16: the kernels fetch 16 bytes per lane
         LKM_TRY_HIP(hipMalloc(&h->s2, h->E * n2 * 4 + 16));
         h->weight_bytes += (int64_t)h->E * (n13 + n2) * 4;
         for (int which = 0; which < 2; ++which) {
-            auto rs13 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4zp(nullptr, sp, dp, dd, gk13, h->spu, which, adt); };
-            auto rs2 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4zp(nullptr, sp, dp, dd, gk2, h->spu, which, adt); };
+            auto rs13 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4zp(nullptr, sp, dp, dd, gk13, h->spu, which, adt, zmask); };
+            auto rs2 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4zp(nullptr, sp, dp, dd, gk2, h->spu, which, adt, zmask); };
             const size_t eb = which ? 1 : 2;       // source bytes per entry: act-dtype scale / uint8 zero point
+            if (which && !w13_gs) {                // symmetric uint8b128: no source, the kernel writes zero point 128
+                LKM_TRY(rs13(nullptr, h->s13, d13));
+                LKM_TRY(rs2(nullptr, h->s2, d2));
+                continue;
+            }
             LKM_TRY(hand_off(which ? w13_gs : w13_scale, (size_t)halves * h->I * (h->H / gk13) * eb, h->s13, n13 * 4, d13, rs13));
             LKM_TRY(hand_off(which ? w2_gs : w2_scale, (size_t)h->H * (h->I / gk2) * eb, h->s2, n2 * 4, d2, rs2));
         }
@@ -619,6 +631,13 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
     // intermediate and an expert's weights inside 2 GiB buffer windows (prefill_kernel_ok); fp8: one scale per 16-row
     // tile and 128-k unit
     const bool w8a16 = h->wf == LKM_W_FP8_E4M3 && !h->a8;
+    // weight-only uint8 (LKM_W_INT8): one byte per weight in the fp8 geometry, so the plan starts from the fp8-W8A16 rules
+    // below (w8b: "a byte per weight, 16-bit activations"), with the register-ring depths of the formats that decode per weight
+    // -- except that decode batches take the tile kernel from 8 tokens on, as the 4-bit formats do (measured, see there).
+    // It takes none of the 4-bit kernels ("pf" 5 / 6 / 7) and has no 256-row tiles: gemm_prefill.h does not decode it, prefill-
+    // sized steps run on the 128-row tile kernel.
+    const bool w8i = h->wf == LKM_W_INT8;
+    const bool w8b = h->wf == LKM_W_FP8_E4M3 || w8i;
     // ... and the 4-bit formats (decoded once per workgroup into the 16-bit image): uint4b8, MXFP4, NVFP4
     const bool w4pf = (h->wf == LKM_W_INT4_B8 && !h->ps && (!h->zp || h->spu <= 2)) || h->wf == LKM_W_MXFP4 || h->wf == LKM_W_NVFP4;   // (not the fast int4 mode: its own image)
     const size_t pf_ub = w4pf ? 1024 : 2048;     // bytes of a (tile, unit) of the image
@@ -661,6 +680,7 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
             // gpu_prefill runs): 128-row tiles x 8 waves from ~100 rows per expert -- int4 Mixtral M=512 725 -> 683 us,
             // M=2048 2159 -> 1951, M=8192 8235 -> 7149 (GEMM1 -21 %); NVFP4 M=2048 2017 -> 1842.  Decode sizes keep 64 / 32.
             if ((h->wf == LKM_W_INT4_B8 || h->wf == LKM_W_NVFP4) && avg_rows >= 96) tiled = 128;
+            if (w8i && avg_rows >= 96) tiled = 128;       // (not measured against 64 rows: int4's threshold, same decode-per-weight kernel)
             // ... and from 112 rows per expert the 256-row prefill kernel with the weights decoded once per workgroup
             // (gemm_prefill.h W4, round 4; Mixtral M=1024 / 2048 / 4096 / 8192, step us: uint4b8 1100 -> 926, 1953 -> 1726, 3696 ->
             // 3068, 7170 -> 5758; NVFP4 M=8192 6677 -> 5723; MXFP4 M=8192 5340 -> 4583: profiles/r04_prefill16_w4.log)
@@ -684,16 +704,20 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
                 h->U1 >= 8 && h->U2 >= 8 && h->U1 <= 64 && h->U2 <= 64 &&
                 h->cfg.groupN % 16 == 0 && h->cfg.groupK == 128 && win_ok)
                 tiled = 256;
-        } else if (h->wf == LKM_W_FP8_E4M3 && M >= 48) {
+        } else if (w8b && M >= 48) {
             // fp8 (both modes): tiles from 48 tokens on (profiles/r01_fp8_tile_threshold.log: Mixtral W8A8
             // M=48 275 -> 265 us, M=64 356 -> 273, M=96 379 -> 281; DSv3 rank slice, 256 rows over 32
             // experts, 280 -> 259; M=16/32 stay with the streamer, 248 vs 261 and 254 vs 260)
             tiled = 64;
-        } else if (wf_is_4bit(h->wf) && M >= 8) {
+        } else if ((wf_is_4bit(h->wf) || w8i) && M >= 8) {
             // 4-bit weights: the tile kernel (token rows staged once per workgroup through LDS, 4 waves x
             // 3 resident workgroups) beats the streamer at EVERY decode batch measured, Mixtral shapes
             // (profiles/r01_4bit_tile_threshold.log): MXFP4 M=8 148 -> 124 us, M=32 166 -> 155, M=64 267 ->
             // 170; int4 M=16 227 -> 196, M=64 300 -> 223; NVFP4 M=32 200 -> 186, M=64 296 -> 213.
+            // ... and so does uint8, whose decoder is no cheaper per fragment (22 VALU, gemm_skinny.h): the streamer decodes every
+            // weight tile once per WAVE for one or two token blocks and is bound by the vector port -- Mixtral uint8b128 M=32,
+            // GEMM1 522 us on the streamer against 282 us for the 16-bit engine on the expanded weights, which reads twice the
+            // bytes (profiles/int8_native_ab.log)
             tiled = 64;
         } else if (M > 16 * tb && h->t_hybrid >= 0) {
             tiled = 64;
@@ -709,7 +733,7 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
             // tiles -- Mixtral W8A8 M=40: 261 -> 256 us uniform, 296 -> 263 Zipf; DSv3 rank slice (32 experts) W8A8 M=32:
             // 168 -> 174 uniform, 132 -> 98 Zipf; W8A16 M=32 / 40: 172 -> 167 / 183 -> 173 uniform, 137 -> 93 / 151 -> 115
             // Zipf.  The streamer half of the hybrid is what skew hurts; no default plan uses the hybrid any more.
-            if (h->wf == LKM_W_FP8_E4M3 && h->t_hybrid == 0) {
+            if (w8b && h->t_hybrid == 0) {
                 tiled = 32;
                 split = 0;
             }
@@ -718,7 +742,7 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
         // the accumulators and two more waves per SIMD resident (profiles/r01_tile32.log: int4 M=16 196 -> 186 us,
         // M=32 196 -> 190, MXFP4 M=32 158 -> 150).  fp8 stays at 64: the DSv3 rank slice loses in GEMM1 (147 ->
         // 160 us) what it gains in GEMM2 (88 -> 85), Mixtral W8A8 M=48 is equal.
-        if (tiled == 64 && !split && wf_is_4bit(h->wf) && est_max <= 32) tiled = 32;
+        if (tiled == 64 && !split && (wf_is_4bit(h->wf) || w8i) && est_max <= 32) tiled = 32;
         // fp8 x fp8 with many experts (round 3, with the four-deep weight ring below): the 32-row tile for the DSv3 rank
         // slice, uniform 266 -> 265 us per step, Zipf (18 of 32 experts hit, the hot one 126 rows) 196 -> 186 (GEMM1 112 ->
         // 102 us: twice the workgroups on a chip the 64-row grid leaves under-subscribed).  W8A16 keeps 64 rows (uniform 263
@@ -736,7 +760,7 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
         // fp8-W8A8 uniform 257 -> 255, Zipf 289 -> 266 (32-row tiles); bf16 M=20 / 24 gain nothing and pay the tile list
         // (+4 us), so the rule starts where two full token blocks are likely (profiles/r03_zipf_launch_order_sweep.log,
         // r03_mixed_plan_sweep.log).  "tiled2" = -1 switches it off, n > 0 forces n-row GEMM2 tiles.
-        if (!tiled && !split && (w16 || h->wf == LKM_W_FP8_E4M3) && est_max >= 24 && h->t_tiled2 >= 0 && h->t_tiled >= 0 &&
+        if (!tiled && !split && (w16 || w8b) && est_max >= 24 && h->t_tiled2 >= 0 && h->t_tiled >= 0 &&
             h->t_fuse == 0)            // ("fuse" = +-1 asks for the streamer GEMM2 with / without the combine folded in)
             g2_only = 32;          // (the rule only holds while an expert cannot exceed 32 rows: one 32-row tile each; against
                                    //  64-row tiles no measurable difference, profiles/r03_headline_gemm2_ab.log)
@@ -779,14 +803,14 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
             pd2 = 4;
             // fp8 with a short K loop (DSv3: I = 2048 = 16 units): four resident waves beat the deeper ring,
             // GEMM2 W8A16 91.3 -> 83.9 us, W8A8 90.8 -> 88.4
-            if (h->wf == LKM_W_FP8_E4M3 && h->U2 <= 32) pd2 = 2;
+            if (w8b && h->U2 <= 32) pd2 = 2;
             if (h->wf == LKM_W_FP8_E4M3 && tiled == 32) pd1 = pd2 = 4;      // (the 32-row tile has the registers for it)
             // int4 / NVFP4 with two GEMM2 tiles per wave: the decoders are VALU-heavy, the resident wave is worth
             // more than the deeper ring (int4 GEMM2 92 -> 84.5 us, NVFP4 80.4 -> 78.6; MXFP4 LOSES: 67.5 -> 72.7)
             if (w4_64 && h->wf != LKM_W_MXFP4) pd2 = 2;
         }
         if (tiled == 128 && waves == 4) pd1 = pd2 = 4;   // EP=8 Mixtral rank: 154 vs 229 us at 2/2
-        int pf = (tiled == 256 && h->t_pf > 0 && !wf_is_4bit(h->wf)) ? h->t_pf : 0;
+        int pf = (tiled == 256 && h->t_pf > 0 && !wf_is_4bit(h->wf) && !w8i) ? h->t_pf : 0;
         // 16-bit weights on 256-row tiles: the 8-phase LDS-DMA kernel (gemm_prefill.h, round 4) is the default -- GLM-4.5-Air
         // bf16 prefill M=8192: GEMM1 1674 -> 1324 us, GEMM2 964 -> 728, step 2919 -> 2227 (profiles/r04_prefill16_*.log);
         // "pf" = -1 keeps gemm_tiled_kernel
@@ -920,7 +944,7 @@ static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   //
     pl->s1 = LaunchCfg{nt1, tb, kw, 1, 0, 0, 0, 0};
     // sub-16-bit weights: two tiles per wave halve the token-operand loads per weight byte
     // (int4 M=32: gemm2 120 us -> 85 us)
-    int nt2 = (wf_is_4bit(h->wf) || h->wf == LKM_W_FP8_E4M3) && tb >= 2 ? 2 : 1;
+    int nt2 = (wf_is_4bit(h->wf) || w8b) && tb >= 2 ? 2 : 1;
     if (tb >= 4 && (long long)n_act * (h->T2 / 2) >= 2 * kMinWaves) nt2 = 2;
     if (h->t_nt2 > 0) nt2 = h->t_nt2;
     int sk = 1;
@@ -1806,7 +1830,7 @@ static void expert_slabs(const LkmEngine* h, int expert, ExpertSlabs* s) {
     if (h->ps) {
         sb13 = t13 * 16 * 4;
         sb2 = t2 * 16 * 4;
-    } else if (h->zp) {
+    } else if (h->zp || h->wf == LKM_W_INT8) {
         sb13 = t13 * 16 * h->spu * 4;
         sb2 = t2 * 16 * h->spu * 4;
     } else if (h->wf == LKM_W_INT4_B8) {

@@ -211,7 +211,7 @@ __device__ __forceinline__ void store1<f16_out>(f16_out* p, float v) {
 // 4 % slower on GEMM2: the loads become 32-byte strided.)  With fp8 ACTIVATIONS (W8A8) one 16-byte
 // token load feeds a PAIR of k-steps: k = unit*128 + pair*64 + g*16 + (0..15).
 //   bf16/f16 : UNITK = 64,  LOADS = 2 (load = kstep),          one dwordx4 = 8 elements
-//   fp8 e4m3 : UNITK = 128, LOADS = 2 (load l: .xy = kstep 2l, .zw = kstep 2l+1; 2 x 8 bytes)
+//   fp8 e4m3 / uint8 : UNITK = 128, LOADS = 2 (load l: .xy = kstep 2l, .zw = kstep 2l+1; 2 x 8 bytes)
 //   uint4b8 / E2M1 (MXFP4, NVFP4) : UNITK = 128, LOADS = 1 (dword s = kstep s), one dwordx4 = 4 x 8 nibbles
 // internal kernel-format code: fp8 weights consumed by the native fp8 MFMA against dynamically
 // quantised fp8 activations (W8A8, the in-tree operator's block-fp8 semantics); same HBM layout as
@@ -241,6 +241,12 @@ struct WGeom<LKM_W_F16> {
 };
 template <>
 struct WGeom<LKM_W_FP8_E4M3> {
+    static constexpr int UNITK = 128, LOADS = 2, KSTEPS = 4;
+};
+// weight-only uint8 (LKM_W_INT8): the fp8 image byte for byte (same repack), the scale image of LKM_W_INT4_ZP below --
+// (scale, zero point) pairs in the activation dtype, zero points 0..255 (exact in bf16 and fp16), 128 when none are given
+template <>
+struct WGeom<LKM_W_INT8> {
     static constexpr int UNITK = 128, LOADS = 2, KSTEPS = 4;
 };
 template <>

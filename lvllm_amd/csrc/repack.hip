@@ -126,9 +126,11 @@ __global__ __launch_bounds__(256) void repack_s_int4_kernel(const unsigned short
 // Two passes over one destination (the hand-off stages one source at a time): which = 0 copies the act-dtype scales
 // src [E][N][K/g] into the even half-words, which = 1 converts the zero points src uint8 [E][N][K/g] (0..15) to the act dtype
 // (exact) into the odd ones.  Padding rows / units: scale 0 (their weights decode to (8 - zp) * 0 = 0).
+// LKM_W_INT8 shares the image: zmask = 255 (a zero point is the whole byte, 0..255 -- still exact in bf16 / fp16), and a null
+// source in pass 1 writes 128 everywhere: symmetric uint8b128 runs the same kernels.
 template <int ADT>
 __global__ __launch_bounds__(256) void repack_s_int4zp_kernel(const void* __restrict__ src, unsigned short* __restrict__ dst,
-                                                              RepackDims d, int group, int spu, int which) {
+                                                              RepackDims d, int group, int spu, int which, int zmask) {
     const size_t n_out = (size_t)d.E * d.halves * d.T_half * d.U * 16 * spu;
     size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= n_out) return;
@@ -149,18 +151,19 @@ __global__ __launch_bounds__(256) void repack_s_int4zp_kernel(const void* __rest
     if (idx < d.n_half && k < d.K) {
         const size_t at = ((size_t)e * N + n) * (d.K / group) + k / group;
         if (which == 0) s = ((const unsigned short*)src)[at];
-        else s = ActT<ADT>::from_f32((float)(((const uint8_t*)src)[at] & 15));
+        else s = ActT<ADT>::from_f32(src ? (float)(((const uint8_t*)src)[at] & zmask) : 128.0f);
     }
     dst[2 * v + which] = s;
 }
 
-int launch_repack_s_int4zp(hipStream_t st, const void* src, void* dst, const RepackDims& d, int group, int spu, int which, int adt) {
+int launch_repack_s_int4zp(hipStream_t st, const void* src, void* dst, const RepackDims& d, int group, int spu, int which, int adt,
+                           int zmask) {
     const size_t n_out = (size_t)d.E * d.halves * d.T_half * d.U * 16 * spu;
     dim3 grid((unsigned)ceil_div64((int64_t)n_out, 256)), block(256);
     if (adt == LKM_DT_BF16)
-        hipLaunchKernelGGL(repack_s_int4zp_kernel<LKM_DT_BF16>, grid, block, 0, st, src, (unsigned short*)dst, d, group, spu, which);
+        hipLaunchKernelGGL(repack_s_int4zp_kernel<LKM_DT_BF16>, grid, block, 0, st, src, (unsigned short*)dst, d, group, spu, which, zmask);
     else
-        hipLaunchKernelGGL(repack_s_int4zp_kernel<LKM_DT_F16>, grid, block, 0, st, src, (unsigned short*)dst, d, group, spu, which);
+        hipLaunchKernelGGL(repack_s_int4zp_kernel<LKM_DT_F16>, grid, block, 0, st, src, (unsigned short*)dst, d, group, spu, which, zmask);
     LKM_HIP_CHECK(hipGetLastError());
     return LKM_OK;
 }
@@ -265,6 +268,7 @@ int launch_repack_w(hipStream_t st, int wf, const void* src, void* dst, const Re
         hipLaunchKernelGGL(repack_w_kernel<LKM_W_F16>, grid, block, 0, st, (const uint8_t*)src, (u32x4*)dst, d);
         break;
     case LKM_W_FP8_E4M3:
+    case LKM_W_INT8:     // one byte per weight: the fp8 byte shuffle (d.a8 = 0)
         hipLaunchKernelGGL(repack_w_kernel<LKM_W_FP8_E4M3>, grid, block, 0, st, (const uint8_t*)src, (u32x4*)dst, d);
         break;
     case LKM_W_INT4_B8:

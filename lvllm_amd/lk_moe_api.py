@@ -33,7 +33,7 @@ from . import _clib
 # gpu_prefill (never under graph capture, :1350-1355).
 _tls = threading.local()
 _FMT = {_clib.W_BF16: "bf16", _clib.W_F16: "fp16", _clib.W_FP8_E4M3: "fp8", _clib.W_INT4_B8: "int4", _clib.W_NVFP4: "nvfp4",
-        _clib.W_MXFP4: "mxfp4"}
+        _clib.W_MXFP4: "mxfp4", _clib.W_INT8: "int8"}
 
 
 @contextlib.contextmanager
@@ -120,7 +120,9 @@ class _MOE:
         ccfg = cfg._to_c(self._WEIGHT_FORMAT, self._ACT_DTYPE)
         ptrs = (w13_ptr, w2_ptr, w13_scale_ptr, w2_scale_ptr, w13_global_scale_ptr, w2_global_scale_ptr)
         # (zero-point experts -- LkmConfig.int4_mode ZP, an extension the reference's lk_moe surface does not have -- stay resident)
-        may_spill = not getattr(_tls, "no_spill", False) and int(getattr(cfg, "int4_mode", 0)) != _clib.INT4_ZP
+        # (... and so do the weight-only 8-bit classes below, for the same reason)
+        may_spill = not getattr(_tls, "no_spill", False) and int(getattr(cfg, "int4_mode", 0)) != _clib.INT4_ZP \
+            and self._WEIGHT_FORMAT != _clib.W_INT8
         cap = hbm_cap_bytes() if may_spill else 0
         too_big = False
         if cap:
@@ -359,6 +361,11 @@ MOE_NVFP4 = _mk("MOE_NVFP4", _clib.W_NVFP4, _clib.DT_BF16, "NVFP4 weights (W4A16
 MOE_NVFP4_FP16 = _mk("MOE_NVFP4_FP16", _clib.W_NVFP4, _clib.DT_F16, "NVFP4 weights (W4A16), fp16 activations")
 MOE_MXFP4 = _mk("MOE_MXFP4", _clib.W_MXFP4, _clib.DT_BF16, "MXFP4 weights (W4A16), bf16 activations")
 MOE_MXFP4_FP16 = _mk("MOE_MXFP4_FP16", _clib.W_MXFP4, _clib.DT_F16, "MXFP4 weights (W4A16), fp16 activations")
+# Extension classes, NOT part of the reference's lk_moe family (and therefore not in __all__): weight-only 8-bit experts, the
+# in-tree operator's int8_w8a16 scheme (fused_moe.py:207-276).  uint8 [E, N, K] + act-dtype scales [E, N, K / groupK]
+# (groupN = 1); the two global-scale slots carry uint8 zero points [E, N, K / groupK], both or neither (0, 0 = uint8b128).
+MOE_W8A16 = _mk("MOE_W8A16", _clib.W_INT8, _clib.DT_BF16, "uint8 group-scaled weights (W8A16), bf16 activations")
+MOE_W8A16_FP16 = _mk("MOE_W8A16_FP16", _clib.W_INT8, _clib.DT_F16, "uint8 group-scaled weights (W8A16), fp16 activations")
 
 __all__ = ["MOEConfigV2", "MOE_BF16", "MOE_FP16", "MOE_FP8", "MOE_FP8_FP16", "MOE_WNA16",
            "MOE_WNA16_FP16", "MOE_NVFP4", "MOE_NVFP4_FP16", "MOE_MXFP4", "MOE_MXFP4_FP16"]

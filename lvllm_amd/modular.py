@@ -42,7 +42,7 @@ def _act_name(activation: Any) -> str:
 class LkmQuant:
     """What the engine needs of a FusedMoEQuantConfig (fused_moe/config.py): the weight format, its scales and
     group / block shape.  `from_vllm` reads the same facts off the reference's object."""
-    fmt: str = "bf16"                    # bf16 | fp16 | int4 | fp8 | mxfp4 | nvfp4 | wna16 (expanded at hand-off)
+    fmt: str = "bf16"                    # bf16 | fp16 | int4 | fp8 | mxfp4 | nvfp4 | wna16 (native or expanded: _engine_for)
     w1_scale: torch.Tensor | None = None
     w2_scale: torch.Tensor | None = None
     group_n: int = 0
@@ -51,7 +51,8 @@ class LkmQuant:
     w2_global_scale: torch.Tensor | None = None
     fp8_mode: int = _clib.FP8_W8A16      # FP8_W8A8: activations quantised 1x128 on the fly (in-tree block-fp8)
     # fmt "wna16": weight-only integers the packed uint4b8 format cannot hold -- zero points and / or 8 bits
-    # (fused_moe.py:207-276).  Expanded once to T((q - zp) * s) by lkm_wna16_expand; the 16-bit engine runs on them.
+    # (fused_moe.py:207-276).  _engine_for hands them to the engine's own zero-point uint4 / uint8 formats where the shape
+    # allows it; otherwise they are expanded once to T((q - zp) * s) by lkm_wna16_expand and the 16-bit engine runs on them.
     weight_bits: int = 4
     w1_zp: torch.Tensor | None = None
     w2_zp: torch.Tensor | None = None
@@ -170,8 +171,10 @@ class LkmExperts:
         if "mxfp4" in w or "nvfp4" in w:
             return a == "none"                              # W4A16
         if "int4" in w or "uint4" in w or "int8" in w or "uint8" in w:
-            # uint4b8 natively; zero-point uint4 and 8-bit weight-only (uint8b128 / uint8 + zp) expanded to 16 bits at
-            # hand-off (LkmQuant fmt "wna16").  Integer ACTIVATIONS (w8a8 int8) are not supported.
+            # uint4b8 and zero-point uint4 natively, 8-bit weight-only (uint8b128 / uint8 + zp) natively with
+            # LKM_WNA16_EXPAND=0; otherwise, and for shapes outside the engine's group rule, expanded to 16 bits at
+            # hand-off (LkmQuant fmt "wna16", _engine_for).  Integer
+            # ACTIVATIONS (w8a8 int8) are not supported.
             return a == "none"
         return False
 
@@ -237,6 +240,15 @@ class LkmExperts:
                     # (LkmConfig.int4_mode = LKM_INT4_ZP); zero points unpacked to one byte per (row, group)
                     fmt, zp1, zp2 = "int4", _unpack_zp4(q.w1_zp), _unpack_zp4(q.w2_zp)
                     w1u, w2u = w1u.view(torch.uint8), w2u.view(torch.uint8)
+                elif q.weight_bits == 8 and os.environ.get("LKM_WNA16_EXPAND") == "0" and self._native_zp_ok(w1u, w2u, q):
+                    # uint8b128 / uint8 + zero points: one byte per weight in HBM, T((q - zp) * s) decoded in registers
+                    # (LKM_W_INT8); 8-bit zero points arrive unpacked [E, N, K / g] (ops.wna16_expand).  OPT-IN on this
+                    # surface, LKM_WNA16_EXPAND=0 ("expand nothing that has a native format"): with the variable unset an
+                    # 8-bit layer keeps the expanded 16-bit engine it has had here since round 6, which
+                    # tests/test_zz6_gpu_reference_modular_kernel.py pins by describe() -- same numbers either way, half the
+                    # bytes and 0.56-0.63 of the step time with the native format (profiles/int8_native_ab.log)
+                    fmt, zp1, zp2 = "int8", q.w1_zp, q.w2_zp
+                    w1u, w2u = w1u.view(torch.uint8), w2u.view(torch.uint8)
             if fmt == "wna16":
                 w1u = ops.wna16_expand(w1u.view(torch.uint8), q.w1_scale, q.w1_zp, q.weight_bits, q.group_k)
                 w2u = ops.wna16_expand(w2u.view(torch.uint8), q.w2_scale, q.w2_zp, q.weight_bits, q.group_k)
@@ -251,10 +263,11 @@ class LkmExperts:
 
     @staticmethod
     def _native_zp_ok(w1u: torch.Tensor, w2u: torch.Tensor, q: LkmQuant) -> bool:
-        """the shapes lkm_create takes in the zero-point mode (include/lkm.h: LkmConfig.groupK for int4); anything else is
-        expanded to 16 bits at hand-off"""
+        """the shapes lkm_create takes in the zero-point mode and for 8-bit weights (include/lkm.h: LkmConfig.groupK for
+        int4); anything else is expanded to 16 bits at hand-off"""
         g = int(q.group_k)
-        k1, k2 = w1u.shape[-1] * 2, w2u.shape[-1] * 2
+        per_byte = 2 if q.weight_bits == 4 else 1
+        k1, k2 = w1u.shape[-1] * per_byte, w2u.shape[-1] * per_byte
         if not (g in (32, 64, 128) or (g > 128 and g % 128 == 0)):
             return False
         return k1 % g == 0 and k2 % g == 0 and k1 % 128 == 0 and k2 % 128 == 0 and os.environ.get("LKM_WNA16_EXPAND", "0") != "1"

@@ -19,7 +19,7 @@ import ctypes as C
 import torch
 
 from . import _clib
-from .lk_moe_api import (MOE_BF16, MOE_FP16, MOE_FP8, MOE_FP8_FP16, MOE_MXFP4, MOE_MXFP4_FP16,
+from .lk_moe_api import (MOE_BF16, MOE_FP16, MOE_FP8, MOE_FP8_FP16, MOE_MXFP4, MOE_MXFP4_FP16, MOE_W8A16, MOE_W8A16_FP16,
                          MOE_NVFP4, MOE_NVFP4_FP16, MOE_WNA16, MOE_WNA16_FP16, MOEConfigV2)
 
 _DT = {torch.float32: _clib.DT_F32, torch.bfloat16: _clib.DT_BF16, torch.float16: _clib.DT_F16}
@@ -414,7 +414,8 @@ _CLS = {("bf16", torch.bfloat16): MOE_BF16, ("bf16", torch.float16): MOE_FP16,
         ("fp8", torch.bfloat16): MOE_FP8, ("fp8", torch.float16): MOE_FP8_FP16,
         ("int4", torch.bfloat16): MOE_WNA16, ("int4", torch.float16): MOE_WNA16_FP16,
         ("mxfp4", torch.bfloat16): MOE_MXFP4, ("mxfp4", torch.float16): MOE_MXFP4_FP16,
-        ("nvfp4", torch.bfloat16): MOE_NVFP4, ("nvfp4", torch.float16): MOE_NVFP4_FP16}
+        ("nvfp4", torch.bfloat16): MOE_NVFP4, ("nvfp4", torch.float16): MOE_NVFP4_FP16,
+        ("int8", torch.bfloat16): MOE_W8A16, ("int8", torch.float16): MOE_W8A16_FP16}
 
 
 class RoutedExpertsEngine:
@@ -434,7 +435,9 @@ class RoutedExpertsEngine:
                  w13_zp: torch.Tensor | None = None, w2_zp: torch.Tensor | None = None):
         """w13_zp / w2_zp (fmt "int4" only): the zero points of asymmetric uint4 experts, uint8 [E, rows, K / group_k], one byte
         (0..15) per weight row and scale group -> LkmConfig.int4_mode = LKM_INT4_ZP, weights dequantised to T((q - zp) * s)
-        (fused_moe.py:272-276); they travel in the global-scale pointer slots of lkm_create (include/lkm.h)."""
+        (fused_moe.py:272-276); they travel in the global-scale pointer slots of lkm_create (include/lkm.h).
+        fmt "int8" (weight-only uint8, LKM_W_INT8: w13 / w2 uint8 [E, rows, K], scales in the activation dtype, group_n = 1)
+        takes them the same way, one byte 0..255 each, both or neither: without them the layer is symmetric uint8b128."""
         E = w13.shape[0]
         H = w2.shape[1]
         inter = w13.shape[1] // (2 if has_gate_proj else 1)
@@ -453,12 +456,13 @@ class RoutedExpertsEngine:
         if (w13_zp is None) != (w2_zp is None):
             raise ValueError("zero points: w13_zp and w2_zp come together")
         if w13_zp is not None:
-            if fmt != "int4" or int4_mode not in (_clib.INT4_EXACT, _clib.INT4_ZP):
-                raise ValueError("zero points belong to fmt='int4' in the exact mode")
+            if fmt not in ("int4", "int8") or int4_mode not in (_clib.INT4_EXACT, _clib.INT4_ZP):
+                raise ValueError("zero points belong to fmt='int4' in the exact mode and to fmt='int8'")
             if w13_zp.dtype != torch.uint8 or w2_zp.dtype != torch.uint8 or tuple(w13_zp.shape) != tuple(w13_scale.shape) \
                     or tuple(w2_zp.shape) != tuple(w2_scale.shape):
                 raise ValueError("zero points: uint8 tensors shaped like the scales ([E, rows, K / group])")
-            int4_mode = _clib.INT4_ZP
+            if fmt == "int4":
+                int4_mode = _clib.INT4_ZP
         elif int4_mode == _clib.INT4_ZP:
             raise ValueError("int4_mode ZP without zero points")
         cfg.int4_mode = int4_mode

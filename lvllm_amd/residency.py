@@ -104,7 +104,7 @@ class TierConfig:
 
 
 # ------------------------------------------------------------------ HBM capacity planning
-_BITS = {"bf16": 16.0, "fp16": 16.0, "fp8": 8.0, "int4": 4.0, "mxfp4": 4.0, "nvfp4": 4.0}
+_BITS = {"bf16": 16.0, "fp16": 16.0, "fp8": 8.0, "int4": 4.0, "mxfp4": 4.0, "nvfp4": 4.0, "int8": 8.0}
 
 
 def expert_layer_bytes(num_local_experts: int, hidden: int, intermediate: int, fmt: str,
@@ -123,6 +123,8 @@ def expert_layer_bytes(num_local_experts: int, hidden: int, intermediate: int, f
         s = units * 4
     elif fmt == "int4":
         s = units * (1 if group_k >= 128 else 128 // group_k) * 2
+    elif fmt == "int8":      # (scale, zero point) pairs in the activation dtype, also for symmetric layers
+        s = units * (1 if group_k >= 128 else 128 // group_k) * 4
     elif fmt == "mxfp4":
         s = units * 4
     elif fmt == "nvfp4":
