@@ -45,7 +45,8 @@ extern "C" {
 #define LKM_W_INT4_B8 3  /* MOE_WNA16[_FP16]  : uint4b8 bytes [E,N,K/2] + act-dtype scales     */
 #define LKM_W_NVFP4 4    /* MOE_NVFP4[_FP16]  : E2M1 bytes [E,N,K/2] + fp8 e4m3fn block scales       *
                           *   [E,N,K/16] (linear) + per-expert f32 multipliers [E] (global)  */
-#define LKM_W_MXFP4 5    /* MOE_MXFP4[_FP16]  : E2M1 bytes [E,N,K/2] + uint8 E8M0 scales [E,N,K/32]  */
+#define LKM_W_MXFP4 5    /* MOE_MXFP4[_FP16]  : E2M1 bytes [E,N,K/2] + uint8 E8M0 scales [E,N,K/32]; fp8_mode 0 = weight-only *
+                          *   (W4A16), LKM_FP8_W8A8 = MXFP8 activations on the scaled MFMA (W4A8, see LKM_FP8_* below)         */
 #define LKM_W_INT8 6     /* weight-only 8 bits (the in-tree operator's int8_w8a16, fused_moe.py:207-276; no lk_moe class): *
                           *   uint8 bytes [E,N,K] + act-dtype scales [E,N,K/group] (groupN == 1, the group rule of         *
                           *   LKM_W_INT4_B8), dequantised to T((q - zp) * s).  Zero points: uint8 [E,N,K/group] in the two  *
@@ -59,6 +60,11 @@ extern "C" {
 /* fp8 compute mode */
 #define LKM_FP8_W8A16 0 /* lk_moe semantics: weight-only fp8, activations stay bf16/fp16      */
 #define LKM_FP8_W8A8 1  /* in-tree operator semantics: dynamic 1 x groupK activation quant     */
+/* With weight_format LKM_W_MXFP4 the field selects the activation side of the MX product: 0 keeps the weight-only path
+ * (16-bit activations), LKM_FP8_W8A8 quantises the hidden states and the intermediate to MXFP8 (1 x 32 blocks: one E8M0
+ * byte + 32 e4m3fn bytes, lkm_quant_mxfp8_rows) and both GEMMs run on v_mfma_scale_f32_16x16x128_f8f6f4 with the
+ * E8M0 scales of both operands applied by the instruction (the reference's mxfp4_mxfp8_moe_quant_config).  Any other
+ * value is LKM_E_INVALID.  Every other weight format but LKM_W_FP8_E4M3 ignores the field. */
 
 /* uint4b8 compute mode */
 #define LKM_INT4_EXACT 0 /* weights dequantised to T((q-8)*s), the reference's rounding (fused_moe.py:237-276)      */
@@ -288,6 +294,14 @@ int lkm_sort_slots(void* stream, const int32_t* ids, int32_t n_slots, int32_t E,
  */
 int lkm_per_token_group_quant_fp8(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
                                   void* q, float* scales);
+
+/* MXFP8 quantisation of activation rows (mxfp8_utils.py:38-85): per 32 columns one E8M0 byte + 32 e4m3fn bytes.
+ * x [rows][ld_x] 16-bit (x_dtype), cols % 32 == 0; q [rows][cols] bytes; scales uint8 [rows][cols / 32] row-major.
+ * Exponent byte = clamp(ceil(log2(amax / 448)) + 127, 0, 254) from the float's own exponent and mantissa (no log2);
+ * amax = 0 gives byte 0 and zero values; values = e4m3fn(x * 2^(127 - byte)), round to nearest even.  The engine runs the
+ * same kernel on the inputs of an LKM_W_MXFP4 / LKM_FP8_W8A8 layer; exposed so that the bytes can be checked. */
+int lkm_quant_mxfp8_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
+                         void* q, uint8_t* scales);
 
 /*
  * Weight-only integer experts of the in-tree operator surface (secondary boundary): int4_w4a16 / int8_w8a16 with or

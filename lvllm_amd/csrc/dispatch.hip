@@ -780,6 +780,81 @@ int launch_quant_fp8_rows(hipStream_t st, const void* src, int ld_src, int adt, 
     return LKM_OK;
 }
 
+// ------------------------------------------------------------------ MXFP8 activation rows (MXFP4 x MXFP8, gemm_mxa8.h)
+// Per row and 32 consecutive columns: one E8M0 byte + 32 e4m3fn bytes (the reference's _mxfp8_e4m3_quantize_torch).
+// One lane owns an aligned 8-column piece (one 16-byte load, one 8-byte store), the four lanes of a block reduce amax
+// with two quad-permute DPP moves.  amax is the integer maximum of the magnitude bits (fp32 order = integer order for
+// non-negative floats; no flush of bf16 subnormals on the way), and the exponent comes from its own fields:
+//   amax = m 2^x, m in [1, 2):  e = ceil(log2(amax / 448)) = x - 8 if m <= 1.75 else x - 7      (448 = 1.75 * 2^8)
+//   byte = clamp(e + 127, 0, 254); amax = 0 -> byte 0.  Values: e4m3fn(x * 2^(127 - byte)) with v_ldexp_f32 (exact; the
+//   factor itself may be subnormal) and v_cvt_pk_fp8_f32 (RNE); |x| 2^-e <= 448 by construction, nothing saturates.
+// PAD = false: the plain row-major form of lkm_quant_mxfp8_rows (q [R][K], scales [R][K / 32]).  PAD = true: the engine's
+// image -- rows padded to whole 128-k units, q [R][Kp], scales [R][Kp / 32] (one aligned dword per row and unit, what
+// a token row of gemm_mxa8_kernel fetches per unit); the pad columns are value 0 with scale byte 127.
+template <int ADT, bool PAD>
+__global__ __launch_bounds__(256) void quant_mxfp8_rows_kernel(const unsigned short* __restrict__ src, long long ld_src, int R,
+                                                               int K, unsigned char* __restrict__ dst,
+                                                               unsigned char* __restrict__ scales) {
+    const int Kp = PAD ? (K + 127) / 128 * 128 : K;
+    const int PPR = Kp >> 3;                                     // 8-column pieces per row (K % 32 == 0)
+    const long long pc = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pc >= (long long)R * PPR) return;                        // (PPR % 4 == 0: the four lanes of a block leave together)
+    const int row = (int)(pc / PPR), k = (int)(pc % PPR) * 8;
+    const bool in = k < K;                                       // a 32-block is wholly inside or wholly pad
+    u32x4 raw = {0u, 0u, 0u, 0u};
+    if (in) raw = *(const u32x4*)(src + (size_t)row * ld_src + k);
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = ActT<ADT>::to_f32((unsigned short)(raw[i] & 0xffffu));
+        v[2 * i + 1] = ActT<ADT>::to_f32((unsigned short)(raw[i] >> 16));
+    }
+    int amax = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int b = __builtin_bit_cast(int, v[i]) & 0x7fffffff;
+        amax = b > amax ? b : amax;
+    }
+    {
+        int o = __builtin_amdgcn_update_dpp(0, amax, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
+        amax = o > amax ? o : amax;
+        o = __builtin_amdgcn_update_dpp(0, amax, 0x4E, 0xf, 0xf, true);          // quad_perm [2,3,0,1]
+        amax = o > amax ? o : amax;
+    }
+    int byte = PAD ? 127 : 0;
+    if (in) {
+        const int x = (amax >> 23) - 127, man = amax & 0x7fffff;
+        const int e = man <= 0x600000 ? x - 8 : x - 7;
+        byte = e + 127;
+        byte = byte < 0 ? 0 : (byte > 254 ? 254 : byte);
+        if (amax == 0) byte = 0;
+    }
+    float q[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) q[i] = __builtin_ldexpf(v[i], 127 - byte);
+    u32x2 o;
+    int pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[0], q[1], 0, false);
+    o.x = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(q[2], q[3], pk, true);
+    pk = __builtin_amdgcn_cvt_pk_fp8_f32(q[4], q[5], 0, false);
+    o.y = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(q[6], q[7], pk, true);
+    *(u32x2*)(dst + (size_t)row * Kp + k) = o;
+    if ((k & 31) == 0) scales[(size_t)row * (Kp >> 5) + (k >> 5)] = (unsigned char)byte;
+}
+
+int launch_quant_mxfp8_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst,
+                            unsigned char* scales, bool pad) {
+    if (R <= 0) return LKM_OK;
+    const int Kp = pad ? (K + 127) / 128 * 128 : K;
+    const long long pieces = (long long)R * (Kp >> 3);
+    dim3 grid((unsigned)((pieces + 255) / 256)), block(256);
+#define LKM_MXQ(ADT_, PAD_) hipLaunchKernelGGL((quant_mxfp8_rows_kernel<ADT_, PAD_>), grid, block, 0, st, (const unsigned short*)src, ld_src, R, K, (unsigned char*)dst, scales)
+    if (adt == LKM_DT_BF16) { if (pad) LKM_MXQ(LKM_DT_BF16, true); else LKM_MXQ(LKM_DT_BF16, false); }
+    else { if (pad) LKM_MXQ(LKM_DT_F16, true); else LKM_MXQ(LKM_DT_F16, false); }
+#undef LKM_MXQ
+    LKM_HIP_CHECK(hipGetLastError());
+    return LKM_OK;
+}
+
 // ------------------------------------------------------------------ 128-element row sums (int4 fast mode)
 // sums[row][kb] = sum of x[row][kb*128 .. +127] in fp32: the activation-side term of
 //   sum_k s (v_k - 8) x_k = s (sum_k (BIAS + v_k) x_k - (BIAS + 8) sum_k x_k)      (lkm_common.h LKM_W_INT4_PS).

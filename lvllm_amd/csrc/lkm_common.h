@@ -228,6 +228,11 @@ __device__ __forceinline__ void store1<f16_out>(f16_out* p, float v) {
 // image; the scale image holds (scale, zero point) PAIRS in the activation dtype -- [tile][unit][16 rows][spu][2] -- and the
 // decoder's addend is -zp * s instead of -8 * s (exact: zp <= 15 times a 16-bit scale has <= 15 significant bits).
 #define LKM_W_INT4_ZP 102
+// internal kernel-format code: MXFP4 weights against MXFP8 activations (LkmConfig.fp8_mode = LKM_FP8_W8A8 with LKM_W_MXFP4) on the
+// scaled MFMA (gemm_mxa8.h).  Its own image: [tile][unit][lane][16 B] with lane (g, i) = row tile*16 + i, k = unit*128 + g*32 +
+// 0..31 -- the 32 k of ONE scale block per lane, where the weight-only image gives a lane pieces of four blocks -- and the E8M0
+// bytes as [tile][unit / 4][lane] dwords (byte j = unit 4q + j), selected by the instruction's op_sel.
+#define LKM_W_MXFP4_A8 103
 
 template <int WF>
 struct WGeom;

@@ -36,6 +36,8 @@ int launch_repack_s_fp8(hipStream_t st, const void* src, void* dst, const Repack
                         int gK);
 int launch_repack_s_fp4(hipStream_t st, const void* src, void* dst, const RepackDims& d, int group,
                         int pad);
+// MXFP4 x MXFP8 (LKM_W_MXFP4_A8): E8M0 scales [E][N][K/32] -> [E][tile][ceil(U / 4)][lane] dwords (gemm_mxa8.h)
+int launch_repack_s_mxa8(hipStream_t st, const void* src, void* dst, const RepackDims& d);
 
 // ---- dispatch.hip
 // Work list of the round-3 fp8 x fp8 prefill kernel: for each of the two GEMMs (rg1 / rg2 row groups per token tile),
@@ -66,6 +68,10 @@ inline int pack_mixed_tiles(int big_rows, int big_min) { return -((big_rows << 1
 constexpr int kMetaInts = 32;   // meta[0..3]: see dispatch.hip; meta[8..16]: per-XCD runs of the tile list
 int launch_quant_fp8_rows(hipStream_t st, const void* src, int ld_src, int adt, int R, int K, void* dst,
                           float* scales);
+// MXFP8 rows (MXFP4 x MXFP8): pad = false -> q [R][K], scales [R][K / 32]; pad = true -> rows padded to whole 128-k units
+// (q [R][Kp], scales [R][Kp / 32], pad columns 0 with scale byte 127): the token image of gemm_mxa8_kernel
+int launch_quant_mxfp8_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst,
+                            unsigned char* scales, bool pad);
 // int4 fast mode: sums[r][kb] = fp32 sum of the 128 elements of group kb of row r (16-bit rows, row stride ld_src)
 int launch_rowsum128_rows(hipStream_t st, const void* src, int ld_src, int adt, int R, int K, float* sums);
 int launch_combine(hipStream_t st, const void* y, int y_dt, int SK, size_t sk_stride,

@@ -231,6 +231,72 @@ __global__ __launch_bounds__(256) void repack_s_fp4_kernel(const uint8_t* __rest
     dst[v] = s;
 }
 
+// MXFP4 x MXFP8 (gemm_mxa8.h): the fp4 operand of v_mfma_scale_f32_16x16x128_f8f6f4 -- lane (g, i) owns the 32 k of ONE scale
+// block, k = unit*128 + g*32 + 0..31, as the 16 source bytes they already are (two E2M1 per byte, even k in the low nibble).
+// Padded rows / K: nibble 0 (= 0.0).
+__global__ __launch_bounds__(256) void repack_w_mxa8_kernel(const uint8_t* __restrict__ src, u32x4* __restrict__ dst, RepackDims d) {
+    const size_t nvec = (size_t)d.E * d.halves * d.T_half * d.U * 64;
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= nvec) return;
+    const int lane = (int)(v & 63);
+    size_t t = v >> 6;
+    const int u = (int)(t % d.U);
+    t /= d.U;
+    const int tile = (int)(t % (d.halves * d.T_half));
+    const int e = (int)(t / (d.halves * d.T_half));
+    const int i = lane & 15, g = lane >> 4;
+    const int half = tile / d.T_half;
+    const int idx = (tile % d.T_half) * 16 + i;
+    const int N = d.n_half * d.halves;
+    const int n = d.interleaved ? idx * d.halves + half : half * d.n_half + idx;
+    const int k0 = u * 128 + g * 32;
+    u32x4 o = {0u, 0u, 0u, 0u};
+    if (idx < d.n_half && k0 < d.K) {                          // K % 32 == 0: the block is whole
+        const uint8_t* p = src + ((size_t)e * N + n) * (d.K / 2) + (k0 >> 1);
+#pragma unroll
+        for (int w = 0; w < 4; ++w)
+            o[w] = (unsigned)p[4 * w] | ((unsigned)p[4 * w + 1] << 8) | ((unsigned)p[4 * w + 2] << 16) | ((unsigned)p[4 * w + 3] << 24);
+    }
+    dst[v] = o;
+}
+
+// ... and its E8M0 scales: src [E][N][K/32] -> dst [E][tile][U4 = ceil(U / 4)][lane] dwords, byte j of lane (g, i) = the scale
+// of (row tile*16 + i, 32-block (4 q + j) * 4 + g); padding rows / blocks / units: 127 (= 1.0; their weights are 0)
+__global__ __launch_bounds__(256) void repack_s_mxa8_kernel(const uint8_t* __restrict__ src, unsigned* __restrict__ dst, RepackDims d) {
+    const int U4 = (d.U + 3) / 4;
+    const size_t n_out = (size_t)d.E * d.halves * d.T_half * U4 * 64;
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v >= n_out) return;
+    const int lane = (int)(v & 63);
+    size_t t = v >> 6;
+    const int q = (int)(t % U4);
+    t /= U4;
+    const int tile = (int)(t % (d.halves * d.T_half));
+    const int e = (int)(t / (d.halves * d.T_half));
+    const int i = lane & 15, g = lane >> 4;
+    const int half = tile / d.T_half;
+    const int idx = (tile % d.T_half) * 16 + i;
+    const int N = d.n_half * d.halves;
+    const int n = d.interleaved ? idx * d.halves + half : half * d.n_half + idx;
+    unsigned o = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = (q * 4 + j) * 128 + g * 32;
+        unsigned b = 127;
+        if (idx < d.n_half && k < d.K) b = src[((size_t)e * N + n) * (d.K / 32) + k / 32];
+        o |= b << (8 * j);
+    }
+    dst[v] = o;
+}
+
+int launch_repack_s_mxa8(hipStream_t st, const void* src, void* dst, const RepackDims& d) {
+    const size_t n_out = (size_t)d.E * d.halves * d.T_half * ((d.U + 3) / 4) * 64;
+    hipLaunchKernelGGL(repack_s_mxa8_kernel, dim3((unsigned)ceil_div64((int64_t)n_out, 256)), dim3(256), 0, st,
+                       (const uint8_t*)src, (unsigned*)dst, d);
+    LKM_HIP_CHECK(hipGetLastError());
+    return LKM_OK;
+}
+
 // fp8 block scales: src fp32 [E][ceil(N/gN)][ceil(K/gK)] -> dst fp32 [E][tile][unit][16 rows]
 __global__ __launch_bounds__(256) void repack_s_fp8_kernel(const float* __restrict__ src,
                                                            float* __restrict__ dst, RepackDims d,
@@ -257,7 +323,7 @@ __global__ __launch_bounds__(256) void repack_s_fp8_kernel(const float* __restri
 }
 
 int launch_repack_w(hipStream_t st, int wf, const void* src, void* dst, const RepackDims& d) {
-    const int loads = wf_loads(wf == LKM_W_INT4_PS ? LKM_W_INT4_B8 : wf);
+    const int loads = wf_loads(wf == LKM_W_INT4_PS ? LKM_W_INT4_B8 : (wf == LKM_W_MXFP4_A8 ? LKM_W_MXFP4 : wf));
     const size_t nvec = (size_t)d.E * d.halves * d.T_half * d.U * loads * 64;
     dim3 grid((unsigned)ceil_div64((int64_t)nvec, 256)), block(256);
     switch (wf) {
@@ -280,6 +346,9 @@ int launch_repack_w(hipStream_t st, int wf, const void* src, void* dst, const Re
     case LKM_W_MXFP4:
     case LKM_W_NVFP4:
         hipLaunchKernelGGL(repack_w_kernel<LKM_W_MXFP4>, grid, block, 0, st, (const uint8_t*)src, (u32x4*)dst, d);
+        break;
+    case LKM_W_MXFP4_A8:
+        hipLaunchKernelGGL(repack_w_mxa8_kernel, grid, block, 0, st, (const uint8_t*)src, (u32x4*)dst, d);
         break;
     default:
         set_error("repack: unsupported weight format %d", wf);

@@ -49,7 +49,8 @@ class LkmQuant:
     group_k: int = 0
     w1_global_scale: torch.Tensor | None = None
     w2_global_scale: torch.Tensor | None = None
-    fp8_mode: int = _clib.FP8_W8A16      # FP8_W8A8: activations quantised 1x128 on the fly (in-tree block-fp8)
+    fp8_mode: int = _clib.FP8_W8A16      # FP8_W8A8: activations quantised on the fly -- fp8: 1x128 (in-tree block-fp8);
+                                         # mxfp4: MXFP8, 1x32 E8M0 blocks (mxfp4_mxfp8_moe_quant_config)
     # fmt "wna16": weight-only integers the packed uint4b8 format cannot hold -- zero points and / or 8 bits
     # (fused_moe.py:207-276).  _engine_for hands them to the engine's own zero-point uint4 / uint8 formats where the shape
     # allows it; otherwise they are expanded once to T((q - zp) * s) by lkm_wna16_expand and the 16-bit engine runs on them.
@@ -86,6 +87,12 @@ class LkmQuant:
                             w1_zp=z1, w2_zp=z2)
         if getattr(qc, "use_mxfp4_w4a16", False):
             return LkmQuant("mxfp4", qc.w1_scale, qc.w2_scale, 1, 32)
+        # MXFP4 weights x dynamically quantised MXFP8 activations (config.py:735-762: _a1 = _a2 = "mxfp8", _w1 = _w2 = "mxfp4")
+        if getattr(qc, "weight_quant_dtype", None) == "mxfp4" and getattr(qc, "quant_dtype", None) == "mxfp8":
+            for name in ("w1_bias", "w2_bias"):
+                if getattr(qc, name, None) is not None:
+                    raise ValueError(f"MXFP4 x MXFP8 experts with {name} are not supported by the MI355X engine")
+            return LkmQuant("mxfp4", qc.w1_scale, qc.w2_scale, 1, 32, fp8_mode=_clib.FP8_W8A8)
         raise ValueError("quantisation scheme of this FusedMoEQuantConfig is not supported by the MI355X engine")
 
 
@@ -168,7 +175,9 @@ class LkmExperts:
             return a == "none"
         if "fp8" in w and "128" in w:                       # kFp8Static128BlockSym x (None | kFp8Dynamic128Sym)
             return a == "none" or ("fp8" in a and "128" in a)
-        if "mxfp4" in w or "nvfp4" in w:
+        if "mxfp4" in w:
+            return a == "none" or "mxfp8" in a              # W4A16, or MXFP8 activations on the scaled MFMA (W4A8)
+        if "nvfp4" in w:
             return a == "none"                              # W4A16
         if "int4" in w or "uint4" in w or "int8" in w or "uint8" in w:
             # uint4b8 and zero-point uint4 natively, 8-bit weight-only (uint8b128 / uint8 + zp) natively with

@@ -269,6 +269,18 @@ def per_token_group_quant_fp8(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tens
     return q, sc
 
 
+def quant_mxfp8_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [rows, cols] bf16 / fp16 (cols a multiple of 32, row stride of 8) -> (q uint8 [rows, cols] e4m3fn bytes, scales uint8
+    [rows, cols / 32] E8M0): the MXFP8 quantiser (mxfp8_utils.py:38-85) the MXFP4 x MXFP8 engines run on their inputs."""
+    _need_cuda(x)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.bfloat16, torch.float16)
+    rows, cols = x.shape
+    q = torch.empty((rows, cols), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+    _clib.check(_clib.lib().lkm_quant_mxfp8_rows(_stream(x), _ptr(x), _DT[x.dtype], x.stride(0), rows, cols, _ptr(q), _ptr(sc)))
+    return q, sc
+
+
 def wna16_expand(qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor | None, weight_bits: int,
                  group: int) -> torch.Tensor:
     """Weight-only integer experts -> 16-bit weights T((q - zp) * s), the in-tree operator's dequantisation
@@ -437,7 +449,10 @@ class RoutedExpertsEngine:
         (0..15) per weight row and scale group -> LkmConfig.int4_mode = LKM_INT4_ZP, weights dequantised to T((q - zp) * s)
         (fused_moe.py:272-276); they travel in the global-scale pointer slots of lkm_create (include/lkm.h).
         fmt "int8" (weight-only uint8, LKM_W_INT8: w13 / w2 uint8 [E, rows, K], scales in the activation dtype, group_n = 1)
-        takes them the same way, one byte 0..255 each, both or neither: without them the layer is symmetric uint8b128."""
+        takes them the same way, one byte 0..255 each, both or neither: without them the layer is symmetric uint8b128.
+        fp8_mode with fmt "mxfp4": FP8_W8A16 (0) keeps the weight-only path; FP8_W8A8 quantises the hidden states and the
+        intermediate to MXFP8 (1 x 32 E8M0 blocks, lkm_quant_mxfp8_rows) and runs both GEMMs on the scaled MFMA
+        (gemm_mxa8_kernel: W4A8, the reference's mxfp4_mxfp8_moe_quant_config)."""
         E = w13.shape[0]
         H = w2.shape[1]
         inter = w13.shape[1] // (2 if has_gate_proj else 1)

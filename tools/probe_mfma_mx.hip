@@ -1,0 +1,79 @@
+// probe_mfma_mx.hip -- stand-alone MI355X probe: operand and scale-lane layout of v_mfma_scale_f32_16x16x128_f8f6f4 with an fp4 A
+// operand (cbsz 4) against an fp8 e4m3 B operand (blgp 0), the mix gemm_mxa8.h runs.  One wavefront; prints
+//   * for every A position (lane group g, nibble n) the B position (lane group g', byte n') it is multiplied with,
+//   * the result with the scale doubled in one lane group at a time, for data in one lane group at a time (A and B side),
+//   * which byte of the scale register each op_sel value selects.
+// Build: hipcc --offload-arch=gfx950 -O2 tools/probe_mfma_mx.hip -o probe_mfma_mx
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+
+typedef __attribute__((ext_vector_type(8))) int i32x8;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
+
+template <int OA>
+__device__ float mx(const i32x8& a, const i32x8& b, int sa, int sb) {
+    const f32x4 d = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(a, b, f32x4{0.f, 0.f, 0.f, 0.f}, 4, 0, OA, sa, 0, sb);
+    float r = d[0];   // lane 0: D[row 0][token 0]
+    asm volatile("" : "+v"(r));      // (keeps the MFMA out of the `lane == 0` blocks below: it needs the whole wavefront)
+    return r;
+}
+
+// out[0..127]: B position of A position p; then floats: [136..139] op_sel 0..3, [140..155] / [156..171] the scale-lane tables of A / B
+__global__ void probe(int* out) {
+    const int lane = threadIdx.x, g = lane >> 4, i = lane & 15;
+    float* fout = (float*)out;
+    for (int pa = 0; pa < 128; ++pa) {
+        i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (i == 0 && g == pa / 32) a[(pa % 32) / 8] = 0x2 << (4 * (pa % 8));          // E2M1 1.0 in nibble pa % 32 of row 0
+        int found = -1;
+        for (int pb = 0; pb < 128; ++pb) {
+            i32x8 b = {0, 0, 0, 0, 0, 0, 0, 0};
+            if (i == 0 && g == pb / 32) b[(pb % 32) / 4] = 0x38 << (8 * (pb % 4));      // e4m3 1.0 in byte pb % 32 of token 0
+            const float d = mx<0>(a, b, 127, 127);
+            if (d != 0.f) found = pb;
+        }
+        if (lane == 0) out[pa] = found;
+    }
+    const i32x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
+    const i32x8 ones_a = {0x22222222, 0x22222222, 0x22222222, 0x22222222, 0, 0, 0, 0};
+    const i32x8 ones_b = {0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838, 0x38383838};
+    for (int gd = 0; gd < 4; ++gd) {                      // data only in lane group gd; scale 2.0 only in lane group gs
+        const i32x8 a = g == gd ? ones_a : zero, b = g == gd ? ones_b : zero;
+        for (int gs = 0; gs < 4; ++gs) {                  // 32 products of 1.0: 32 without, 64 with the doubled scale
+            const float da = mx<0>(a, ones_b, g == gs ? 128 : 127, 127);
+            const float db = mx<0>(ones_a, b, 127, g == gs ? 128 : 127);
+            if (lane == 0) { fout[140 + gd * 4 + gs] = da; fout[156 + gd * 4 + gs] = db; }
+        }
+    }
+    const int sc = 127 | (128 << 8) | (129 << 16) | (130 << 24);
+    const float d0 = mx<0>(ones_a, ones_b, sc, 127), d1 = mx<1>(ones_a, ones_b, sc, 127), d2 = mx<2>(ones_a, ones_b, sc, 127),
+                d3 = mx<3>(ones_a, ones_b, sc, 127);
+    if (lane == 0) {
+        fout[136] = d0; fout[137] = d1; fout[138] = d2; fout[139] = d3;      // 128 products: 128 x 2^(byte - 127)
+    }
+}
+
+int main() {
+    int* d = nullptr;
+    int h[172];
+    if (hipMalloc(&d, sizeof(h)) != hipSuccess) return 1;
+    hipLaunchKernelGGL(probe, dim3(1), dim3(64), 0, 0, d);
+    hipError_t err = hipGetLastError();
+    if (err == hipSuccess) err = hipDeviceSynchronize();
+    if (err != hipSuccess || hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) {
+        fprintf(stderr, "probe_mfma_mx: kernel did not complete: %s\n", hipGetErrorString(err));
+        return 1;
+    }
+    printf("A (group, nibble) -> B (group, byte):\n");
+    for (int p = 0; p < 128; ++p) printf("(%d,%2d)->(%d,%2d)%s", p / 32, p % 32, h[p] / 32, h[p] % 32, p % 8 == 7 ? "\n" : " ");
+    const float* f = (const float*)h;
+    for (int side = 0; side < 2; ++side)
+        for (int gd = 0; gd < 4; ++gd) {
+            printf("%c data in lane group %d, scale 2.0 in lane group 0..3:", side ? 'B' : 'A', gd);
+            for (int gs = 0; gs < 4; ++gs) printf(" %g", f[140 + side * 16 + gd * 4 + gs]);
+            printf("\n");
+        }
+    printf("scale register bytes 1, 2, 4, 8 (x 128 products), op_sel 0..3: %g %g %g %g\n", f[136], f[137], f[138], f[139]);
+    (void)hipFree(d);
+    return 0;
+}
