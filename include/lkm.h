@@ -50,7 +50,10 @@ extern "C" {
 #define LKM_W_INT8 6     /* weight-only 8 bits (the in-tree operator's int8_w8a16, fused_moe.py:207-276; no lk_moe class): *
                           *   uint8 bytes [E,N,K] + act-dtype scales [E,N,K/group] (groupN == 1, the group rule of         *
                           *   LKM_W_INT4_B8), dequantised to T((q - zp) * s).  Zero points: uint8 [E,N,K/group] in the two  *
-                          *   global-scale pointer slots; both NULL = symmetric uint8b128 (zp = 128)                        */
+                          *   global-scale pointer slots; both NULL = symmetric uint8b128 (zp = 128).                       *
+                          *   fp8_mode LKM_FP8_W8A8 = W8A8-int8 (int8_w8a8_moe_quant_config, per-token activations): SIGNED  *
+                          *   int8 bytes [E,N,K] + fp32 scales [E,N] (or [E,N,1]), one per weight row (groupN == 1, groupK  *
+                          *   >= max(hidden, intermediate)), no zero points; see LKM_FP8_* below                            */
 
 /* MOEConfigV2.activation_type (routed_experts.py:160-164) */
 #define LKM_ACT_SILU 0
@@ -64,7 +67,12 @@ extern "C" {
  * (16-bit activations), LKM_FP8_W8A8 quantises the hidden states and the intermediate to MXFP8 (1 x 32 blocks: one E8M0
  * byte + 32 e4m3fn bytes, lkm_quant_mxfp8_rows) and both GEMMs run on v_mfma_scale_f32_16x16x128_f8f6f4 with the
  * E8M0 scales of both operands applied by the instruction (the reference's mxfp4_mxfp8_moe_quant_config).  Any other
- * value is LKM_E_INVALID.  Every other weight format but LKM_W_FP8_E4M3 ignores the field. */
+ * value is LKM_E_INVALID.
+ * With weight_format LKM_W_INT8 it selects integer activations: 0 keeps the weight-only path, LKM_FP8_W8A8 quantises the
+ * hidden states and the intermediate per token to int8 (scale = amax / 127, lkm_quant_int8_rows) and both GEMMs run on
+ * v_mfma_i32_16x16x64_i8 with exact int32 sums; the token scale and the weight row's scale meet the sum once, in the
+ * epilogue (hidden and intermediate sizes multiples of 32, at most 131072).  Any other value is LKM_E_INVALID.
+ * The remaining weight formats (all but LKM_W_FP8_E4M3, LKM_W_MXFP4 and LKM_W_INT8) ignore the field. */
 
 /* uint4b8 compute mode */
 #define LKM_INT4_EXACT 0 /* weights dequantised to T((q-8)*s), the reference's rounding (fused_moe.py:237-276)      */
@@ -302,6 +310,14 @@ int lkm_per_token_group_quant_fp8(void* stream, const void* x, int32_t x_dtype, 
  * same kernel on the inputs of an LKM_W_MXFP4 / LKM_FP8_W8A8 layer; exposed so that the bytes can be checked. */
 int lkm_quant_mxfp8_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
                          void* q, uint8_t* scales);
+
+/* Dynamic per-token int8 quantisation of activation rows (the reference's dynamic_scaled_int8_quant, scaled_quant.cu): per row
+ * in fp32 amax = max |x|, scales[row] = amax / 127, q = sat_int8(rint(x * (amax == 0 ? 0 : 127 / amax))), ties to even; both
+ * quotients are IEEE divisions, the product is one fp32 multiply.  x [rows][ld_x] 16-bit (x_dtype), cols % 32 == 0 and
+ * <= 131072; q int8 [rows][cols]; scales fp32 [rows].  The engine runs the same kernel on the inputs of an LKM_W_INT8 /
+ * LKM_FP8_W8A8 layer; exposed so that the bytes can be checked. */
+int lkm_quant_int8_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
+                        void* q, float* scales);
 
 /*
  * Weight-only integer experts of the in-tree operator surface (secondary boundary): int4_w4a16 / int8_w8a16 with or

@@ -82,6 +82,8 @@ _SIGS = {
                                               C.c_void_p, C.c_void_p]),
     "lkm_quant_mxfp8_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
+    "lkm_quant_int8_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                    C.c_void_p, C.c_void_p]),
     "lkm_wna16_expand": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32,
                                  C.c_int32, C.c_int32, C.c_int32]),
     "lkm_pointer_is_device": (C.c_int, [C.c_void_p]),

@@ -855,6 +855,106 @@ int launch_quant_mxfp8_rows(hipStream_t st, const void* src, long long ld_src, i
     return LKM_OK;
 }
 
+// ------------------------------------------------------------------ per-token int8 activation rows (int8 x int8, gemm_i8a8.h)
+// The reference's dynamic per-token quantiser (scaled_quant.cu dynamic_scaled_int8_quant_kernel), per row in fp32:
+//   amax = max |x|; scale = amax / 127; inv = amax == 0 ? 0 : 127 / amax; q = sat_i8(rint(float(x) * inv))   (ties to even)
+// The two quotients are IEEE divisions (__fdiv_rn, once per row: no v_rcp_f32), the product is one v_mul_f32 per element with
+// nothing to fuse into, so the bytes are a statement of the inputs alone.  ONE pass: a lane keeps its PPT 16-byte pieces of
+// the row in registers between the reduction and the conversion.  amax is the integer maximum of the magnitude bits (fp32
+// order = integer order for non-negative floats), reduced over a wave with four DPP moves + four lane reads, over a
+// workgroup through LDS.  WAVE_ROW: one row per WAVE (rows of at most 64 * PPT pieces: no LDS, no barrier); otherwise one
+// row per workgroup of THREADS.  PAD: the engine's image -- q rows padded to whole 128-k units with zero bytes.
+__device__ __forceinline__ int wave_max_bits(int v) {
+    int o = __builtin_amdgcn_update_dpp(0, v, 0xB1, 0xf, 0xf, true);             // quad_perm [1,0,3,2]
+    v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x4E, 0xf, 0xf, true);                 // quad_perm [2,3,0,1]
+    v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x141, 0xf, 0xf, true);                // row_half_mirror
+    v = o > v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, 0x140, 0xf, 0xf, true);                // row_mirror: every lane of a 16-row holds its maximum
+    v = o > v ? o : v;
+    const int a = __builtin_amdgcn_readlane(v, 0), b = __builtin_amdgcn_readlane(v, 16), c = __builtin_amdgcn_readlane(v, 32),
+              d = __builtin_amdgcn_readlane(v, 48);
+    const int ab = a > b ? a : b, cd = c > d ? c : d;
+    return ab > cd ? ab : cd;
+}
+
+template <int ADT, bool PAD, int THREADS, int PPT, bool WAVE_ROW>
+__global__ __launch_bounds__(THREADS) void quant_int8_rows_kernel(const unsigned short* __restrict__ src, long long ld_src, int R,
+                                                                  int K, unsigned char* __restrict__ dst, float* __restrict__ scales) {
+    constexpr int WAVES = THREADS / 64, STEP = WAVE_ROW ? 64 : THREADS;
+    __shared__ int wmax[WAVES];
+    const int Kp = PAD ? (K + 127) / 128 * 128 : K;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int row = WAVE_ROW ? blockIdx.x * WAVES + wave : blockIdx.x;
+    const int first = WAVE_ROW ? lane : tid;
+    if (WAVE_ROW && row >= R) return;                       // (wave-uniform; no barrier on this path)
+    const unsigned short* x = src + (size_t)row * ld_src;
+    u32x4 raw[PPT];
+    int amax = 0;
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+        const int k = (first + i * STEP) * 8;
+        raw[i] = u32x4{0u, 0u, 0u, 0u};
+        if (k < K) raw[i] = *(const u32x4*)(x + k);
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int lo = __builtin_bit_cast(int, ActT<ADT>::to_f32((unsigned short)(raw[i][w] & 0xffffu))) & 0x7fffffff;
+            const int hi = __builtin_bit_cast(int, ActT<ADT>::to_f32((unsigned short)(raw[i][w] >> 16))) & 0x7fffffff;
+            amax = lo > amax ? lo : amax;
+            amax = hi > amax ? hi : amax;
+        }
+    }
+    amax = wave_max_bits(amax);
+    if constexpr (!WAVE_ROW) {
+        if (lane == 0) wmax[wave] = amax;
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) amax = wmax[w] > amax ? wmax[w] : amax;
+    }
+    const float am = __builtin_bit_cast(float, amax);
+    const float inv = amax == 0 ? 0.0f : __fdiv_rn(127.0f, am);
+    if (first == 0) scales[row] = __fdiv_rn(am, 127.0f);
+#pragma unroll
+    for (int i = 0; i < PPT; ++i) {
+        const int k = (first + i * STEP) * 8;
+        if (k >= Kp) continue;
+        unsigned o[2] = {0u, 0u};                           // (pieces of [K, Kp): the zero raw bytes give zero)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const float lo = ActT<ADT>::to_f32((unsigned short)(raw[i][w] & 0xffffu)) * inv;
+            const float hi = ActT<ADT>::to_f32((unsigned short)(raw[i][w] >> 16)) * inv;
+            const int ql = (int)__builtin_amdgcn_fmed3f(__builtin_rintf(lo), -128.0f, 127.0f);
+            const int qh = (int)__builtin_amdgcn_fmed3f(__builtin_rintf(hi), -128.0f, 127.0f);
+            o[w >> 1] |= ((unsigned)(ql & 0xff) | ((unsigned)(qh & 0xff) << 8)) << (16 * (w & 1));
+        }
+        *(u32x2*)(dst + (size_t)row * Kp + k) = u32x2{o[0], o[1]};
+    }
+}
+
+int launch_quant_int8_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst, float* scales,
+                           bool pad) {
+    if (R <= 0) return LKM_OK;
+    const int pieces = (pad ? (K + 127) / 128 * 128 : K) >> 3;
+    LKM_REQUIRE(K > 0 && K % 32 == 0 && pieces <= 1024 * 16, "quant_int8_rows: cols=%d (a multiple of 32, at most 131072)", K);
+    // the kernel's 16-byte row loads and 8-byte stores
+    LKM_REQUIRE(ld_src >= K && ld_src % 8 == 0 && ((uintptr_t)src & 15) == 0 && ((uintptr_t)dst & 7) == 0,
+                "quant_int8_rows: ld=%lld (at least cols, a multiple of 8), src 16-byte and dst 8-byte aligned", ld_src);
+#define LKM_I8Q3(ADT_, PAD_, TH_, PPT_, WR_) hipLaunchKernelGGL((quant_int8_rows_kernel<ADT_, PAD_, TH_, PPT_, WR_>), dim3((unsigned)((WR_) ? (R + (TH_) / 64 - 1) / ((TH_) / 64) : R)), dim3(TH_), 0, st, (const unsigned short*)src, ld_src, R, K, (unsigned char*)dst, scales)
+#define LKM_I8Q2(ADT_, PAD_)                                                                                    \
+    do {                                                                                                        \
+        if (pieces <= 64 * 4) LKM_I8Q3(ADT_, PAD_, 256, 4, true);            /* <= 2048 columns: a wave per row */ \
+        else if (pieces <= 256 * 4) LKM_I8Q3(ADT_, PAD_, 256, 4, false);     /* <= 8192 */                        \
+        else LKM_I8Q3(ADT_, PAD_, 1024, 16, false);                                                             \
+    } while (0)
+    if (adt == LKM_DT_BF16) { if (pad) LKM_I8Q2(LKM_DT_BF16, true); else LKM_I8Q2(LKM_DT_BF16, false); }
+    else { if (pad) LKM_I8Q2(LKM_DT_F16, true); else LKM_I8Q2(LKM_DT_F16, false); }
+#undef LKM_I8Q2
+#undef LKM_I8Q3
+    LKM_HIP_CHECK(hipGetLastError());
+    return LKM_OK;
+}
+
 // ------------------------------------------------------------------ 128-element row sums (int4 fast mode)
 // sums[row][kb] = sum of x[row][kb*128 .. +127] in fp32: the activation-side term of
 //   sum_k s (v_k - 8) x_k = s (sum_k (BIAS + v_k) x_k - (BIAS + 8) sum_k x_k)      (lkm_common.h LKM_W_INT4_PS).

@@ -27,6 +27,11 @@ int launch_gemm1_tiled_mxa8_bf16(hipStream_t, const LaunchCfg&, const GemmParams
 int launch_gemm2_tiled_mxa8_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
 int launch_gemm1_tiled_mxa8_f16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
 int launch_gemm2_tiled_mxa8_f16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
+// int8 x per-token int8 on the integer MFMA (gemm_i8a8.h): likewise one family of tile kernels
+int launch_gemm1_tiled_i8a8_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
+int launch_gemm2_tiled_i8a8_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
+int launch_gemm1_tiled_i8a8_f16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
+int launch_gemm2_tiled_i8a8_f16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
 
 // round 4: the 32x32-MFMA kernels of the 4-bit formats (gemm_w4x.h: cfg.pf == 5; gemm_w4e.h, loader wave: cfg.pf == 6;
 // round 6: gemm_w4s.h, token loader wave + register-streamed weights: cfg.pf == 7);
@@ -131,6 +136,7 @@ int launch_gemm1_tiled(hipStream_t st, int wf, int adt, const LaunchCfg& cfg, co
         if (launch_w4x(st, wf, adt, cfg, p, gated, true, max_tiles, &rc)) return rc;
     }
     if (wf == LKM_W_MXFP4_A8) return adt == LKM_DT_BF16 ? launch_gemm1_tiled_mxa8_bf16(st, cfg, p, gated, max_tiles) : launch_gemm1_tiled_mxa8_f16(st, cfg, p, gated, max_tiles);
+    if (wf == LKM_W_INT8_A8) return adt == LKM_DT_BF16 ? launch_gemm1_tiled_i8a8_bf16(st, cfg, p, gated, max_tiles) : launch_gemm1_tiled_i8a8_f16(st, cfg, p, gated, max_tiles);
     if (wf == LKM_W_BF16 && adt == LKM_DT_BF16) return launch_gemm1_tiled_bf16(st, cfg, p, gated, max_tiles);
     if (wf == LKM_W_F16 && adt == LKM_DT_F16) return launch_gemm1_tiled_f16(st, cfg, p, gated, max_tiles);
     if (wf == LKM_W_INT4_B8 && adt == LKM_DT_BF16) return launch_gemm1_tiled_int4_bf16(st, cfg, p, gated, max_tiles);
@@ -161,6 +167,7 @@ int launch_gemm2_tiled(hipStream_t st, int wf, int adt, const LaunchCfg& cfg, co
         if (launch_w4x(st, wf, adt, cfg, p, false, false, max_tiles, &rc)) return rc;
     }
     if (wf == LKM_W_MXFP4_A8) return adt == LKM_DT_BF16 ? launch_gemm2_tiled_mxa8_bf16(st, cfg, p, max_tiles) : launch_gemm2_tiled_mxa8_f16(st, cfg, p, max_tiles);
+    if (wf == LKM_W_INT8_A8) return adt == LKM_DT_BF16 ? launch_gemm2_tiled_i8a8_bf16(st, cfg, p, max_tiles) : launch_gemm2_tiled_i8a8_f16(st, cfg, p, max_tiles);
     if (wf == LKM_W_BF16 && adt == LKM_DT_BF16) return launch_gemm2_tiled_bf16(st, cfg, p, max_tiles);
     if (wf == LKM_W_F16 && adt == LKM_DT_F16) return launch_gemm2_tiled_f16(st, cfg, p, max_tiles);
     if (wf == LKM_W_INT4_B8 && adt == LKM_DT_BF16) return launch_gemm2_tiled_int4_bf16(st, cfg, p, max_tiles);

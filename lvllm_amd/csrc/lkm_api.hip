@@ -170,6 +170,8 @@ struct LkmEngine {
     bool a8;
     bool mx8;                  // MXFP4 weights x MXFP8 activations (fp8_mode W8A8 with LKM_W_MXFP4): kernel format LKM_W_MXFP4_A8, its own
                                // weight / scale image, both GEMMs on gemm_mxa8_kernel (every step size is one of its tile heights)
+    bool i8a;                  // int8 weights x per-token int8 activations (fp8_mode W8A8 with LKM_W_INT8): kernel format LKM_W_INT8_A8, the fp8
+                               // W8A8 weight image + one fp32 scale per weight row, both GEMMs on gemm_i8a8_kernel
     bool zp;                   // uint4 with zero points (int4_mode ZP): (scale, zero point) pairs in the scale image, kernel format LKM_W_INT4_ZP
     bool ps;                   // int4 fast mode: per-(row, 128-k) activation sums feed the GEMMs (arena xqs / aqs)
     // geometry
@@ -378,7 +380,18 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         // MXFP4: fp8_mode selects the activation side -- 0 weight-only (16-bit activations), W8A8 = MXFP8 activations (include/lkm.h)
         LKM_REQUIRE(wf != LKM_W_MXFP4 || cfg->fp8_mode == 0 || cfg->fp8_mode == LKM_FP8_W8A8, "lkm_create: bad fp8_mode %d for MXFP4 (0 = weight-only, %d = MXFP8 activations)", cfg->fp8_mode, LKM_FP8_W8A8);
     }
-    if (wf == LKM_W_INT4_B8 || wf == LKM_W_INT8) {      // weight-only integers: one group rule
+    const bool i8a = wf == LKM_W_INT8 && cfg->fp8_mode == LKM_FP8_W8A8;
+    if (wf == LKM_W_INT8) LKM_REQUIRE(cfg->fp8_mode == 0 || i8a, "lkm_create: bad fp8_mode %d for int8 (0 = weight-only, %d = per-token int8 activations)", cfg->fp8_mode, LKM_FP8_W8A8);
+    if (i8a) {      // int8 x per-token int8 (W8A8): signed bytes, one fp32 scale per weight row, no zero points
+        LKM_REQUIRE(w13_scale && w2_scale, "lkm_create: int8 weights need scales");
+        LKM_REQUIRE(cfg->groupN == 1 && cfg->groupK >= cfg->hidden_size && cfg->groupK >= cfg->intermediate_size,
+                    "lkm_create: int8 with fp8_mode=%d takes one scale per weight row: groupN == 1 and groupK >= max(hidden %d, intermediate %d) (got groupN=%d groupK=%d)",
+                    LKM_FP8_W8A8, cfg->hidden_size, cfg->intermediate_size, cfg->groupN, cfg->groupK);
+        LKM_REQUIRE(!w13_gs && !w2_gs, "lkm_create: int8 with fp8_mode=%d is symmetric: zero points (the two global-scale pointer slots) must be NULL", LKM_FP8_W8A8);
+        LKM_REQUIRE(cfg->hidden_size % 32 == 0 && cfg->intermediate_size % 32 == 0 && cfg->hidden_size <= 131072 && cfg->intermediate_size <= 131072,
+                    "lkm_create: int8 with fp8_mode=%d needs hidden and intermediate sizes that are multiples of 32 and at most 131072 (int32 sums)", LKM_FP8_W8A8);
+    }
+    if (wf == LKM_W_INT4_B8 || (wf == LKM_W_INT8 && !i8a)) {      // weight-only integers: one group rule
         const char* nm = wf == LKM_W_INT8 ? "int8" : "int4";
         LKM_REQUIRE(w13_scale && w2_scale, "lkm_create: %s weights need scales", nm);
         LKM_REQUIRE(cfg->groupN == 1, "lkm_create: %s expects groupN == 1 (got %d)", nm, cfg->groupN);
@@ -423,14 +436,15 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
     h->ps = wf == LKM_W_INT4_B8 && cfg->int4_mode == LKM_INT4_FAST;
     h->zp = wf == LKM_W_INT4_B8 && cfg->int4_mode == LKM_INT4_ZP;
     h->mx8 = wf == LKM_W_MXFP4 && cfg->fp8_mode == LKM_FP8_W8A8;
-    h->wfk = h->a8 ? LKM_W_FP8_A8 : (h->ps ? LKM_W_INT4_PS : (h->zp ? LKM_W_INT4_ZP : (h->mx8 ? LKM_W_MXFP4_A8 : wf)));
+    h->i8a = i8a;
+    h->wfk = h->a8 ? LKM_W_FP8_A8 : (h->ps ? LKM_W_INT4_PS : (h->zp ? LKM_W_INT4_ZP : (h->mx8 ? LKM_W_MXFP4_A8 : (i8a ? LKM_W_INT8_A8 : wf))));
     h->unitk = wf_unitk(wf);
     h->T1_half = round_up(ceil_div(h->I, 16), 4);
     h->U1 = ceil_div(h->H, h->unitk);
     h->T2 = round_up(ceil_div(h->H, 16), 4);
     h->U2 = ceil_div(h->I, h->unitk);
     h->ld_act = h->I;
-    h->spu = (wf == LKM_W_INT4_B8 || wf == LKM_W_INT8) ? (gk13 >= 128 ? 1 : 128 / gk13) : 0;
+    h->spu = (wf == LKM_W_INT4_B8 || (wf == LKM_W_INT8 && !i8a)) ? (gk13 >= 128 ? 1 : 128 / gk13) : 0;
 
     const int loads = wf_loads(wf);
     const int halves = gated ? 2 : 1;
@@ -462,8 +476,8 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
 
     h->loads = loads;
     // (source dims are the caller's: K = Hu for w13, Hu rows for w2 -- the repack kernels bound every element read)
-    RepackDims d13{h->E, h->I, halves, h->interleaved ? 1 : 0, h->Hu, h->T1_half, h->U1, h->a8 ? 1 : 0};
-    RepackDims d2{h->E, h->Hu, 1, 0, h->I, h->T2, h->U2, h->a8 ? 1 : 0};
+    RepackDims d13{h->E, h->I, halves, h->interleaved ? 1 : 0, h->Hu, h->T1_half, h->U1, (h->a8 || i8a) ? 1 : 0};
+    RepackDims d2{h->E, h->Hu, 1, 0, h->I, h->T2, h->U2, (h->a8 || i8a) ? 1 : 0};
     // hand-off of the caller's tensors: device sources are read in place; host sources pass through ONE
     // staging buffer of <= LKM_STAGE_BYTES (default 256 MiB, never less than one expert) in chunks of whole experts --
     // copy, repack, next chunk, all in stream order -- so creation adds at most one chunk to the footprint of the
@@ -504,6 +518,17 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         auto rs2 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4ps(nullptr, sp, dp, dd, gk2, adt); };
         LKM_TRY(hand_off(w13_scale, (size_t)halves * h->I * (h->H / gk13) * 2, h->s13, n13 * 4, d13, rs13));
         LKM_TRY(hand_off(w2_scale, (size_t)h->H * (h->I / gk2) * 2, h->s2, n2 * 4, d2, rs2));
+    } else if (i8a) {          // one fp32 scale per weight row, [tiles * 16] per expert (padded rows 0): the fp8 scale repack with ONE unit and
+                               // one group along K -- the source [E][N] (or [E][N][1]) is its [E][N / 1][1] block-scale form
+        const size_t n13 = (size_t)halves * h->T1_half * 16, n2 = (size_t)h->T2 * 16;
+        LKM_TRY_HIP(hipMalloc(&h->s13, h->E * n13 * 4));
+        LKM_TRY_HIP(hipMalloc(&h->s2, h->E * n2 * 4));
+        h->weight_bytes += (int64_t)h->E * (n13 + n2) * 4;
+        RepackDims s13d = d13, s2d = d2;
+        s13d.U = s2d.U = 1;
+        auto rs13 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_fp8(nullptr, sp, dp, dd, 1, dd.K); };
+        LKM_TRY(hand_off(w13_scale, (size_t)halves * h->I * 4, h->s13, n13 * 4, s13d, rs13));
+        LKM_TRY(hand_off(w2_scale, (size_t)h->H * 4, h->s2, n2 * 4, s2d, rs13));
     } else if (h->zp || wf == LKM_W_INT8) {     // (scale, zero point) pairs: two passes over one image, the zero points from the global-scale slots
         const int zmask = wf == LKM_W_INT8 ? 255 : 15;
         const size_t n13 = (size_t)halves * h->T1_half * h->U1 * 16 * h->spu, n2 = (size_t)h->T2 * h->U2 * 16 * h->spu;
@@ -584,12 +609,13 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         const size_t kb1 = ceil_div(h->H, 128), kb2 = ceil_div(h->I, 128);
         const bool xs = h->a8 || h->ps || h->mx8;       // per-(row, 128-k) scalars: activation scales / activation sums / (MXFP8) one
                                                         // dword of four E8M0 bytes -- the same four bytes per row and unit
+        const bool q8 = h->mx8 || i8a;                  // 8-bit activation rows padded to whole units (int8: + ONE fp32 scale per row)
         // the fp8 x fp8 prefill kernel's item lists: (256-row token tiles of the largest chunk) x (row groups of GEMM1 + GEMM2)
         const size_t items_n = h->a8 ? (slots / 256 + (size_t)h->E + 8) * (size_t)(a8w_row_groups(h, 1) + a8w_row_groups(h, 2)) * 4 : 0;
         LKM_TRY(arena_reserve(h->device, h->E, slots, slots * h->ld_act, y_rows * h->H,
-                              h->a8 ? cap * h->H : (h->mx8 ? cap * kb1 * 128 : 0), xs ? cap * kb1 : 0,      // (MXFP8 rows: whole units)
-                              h->a8 ? slots * h->I : (h->mx8 ? slots * kb2 * 128 : 0),
-                              xs ? slots * kb2 : 0, items_n, &h->arena));
+                              h->a8 ? cap * h->H : (q8 ? cap * kb1 * 128 : 0), xs ? cap * kb1 : (i8a ? cap : 0),
+                              h->a8 ? slots * h->I : (q8 ? slots * kb2 * 128 : 0),
+                              xs ? slots * kb2 : (i8a ? slots : 0), items_n, &h->arena));
     }
     if (h->Hu != h->H) {       // aligned scratch rows for the token and output matrices of one chunk
         LKM_TRY_HIP(hipMalloc(&h->pad_x, cap * (size_t)h->H * 2));
@@ -647,8 +673,34 @@ static void pick_cfg_mx8(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {
     pl->t2 = LaunchCfg{1, tiled / 16, 1, sk2, tiled, 4, 2, 10};
 }
 
+// int8 x per-token int8: likewise one kernel family (gemm_i8a8.h) -- a token-tile height by rows per expert and GEMM2's split-K in
+// whole units; "tiled" < 0 and every "pf" are ignored, a forced height is rounded to the next built one.  Heights: the 8-bit
+// tile rules of the fp8 W8A8 mode (32 rows while an expert is unlikely to hold more, 64, 128 from 64 rows per expert, the
+// prefill height from 192).  Split-K: up to 4 slabs of at least two units while the grid leaves CUs idle.
+static void pick_cfg_i8a(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {
+    const size_t n_eff = h->t_valid_den > 1 ? (n_slots + h->t_valid_den - 1) / h->t_valid_den : n_slots;
+    const int n_act = (int)((size_t)h->E < n_eff ? (size_t)h->E : n_eff);
+    const size_t avg_rows = n_eff / (size_t)(n_act > 0 ? n_act : 1);
+    if (h->t_valid_den > 1) M = (int)((size_t)M < n_eff ? (size_t)M : n_eff);
+    const size_t est_max = (size_t)M < 2 * avg_rows + 8 ? (size_t)M : 2 * avg_rows + 8;
+    int tiled = est_max <= 32 ? 32 : (avg_rows < 64 ? 64 : (avg_rows < 192 ? 128 : 256));
+    if (h->t_tiled > 0) tiled = h->t_tiled <= 32 ? 32 : (h->t_tiled <= 64 ? 64 : (h->t_tiled <= 128 ? 128 : 256));
+    int sk2 = 1;
+    {
+        const long long wg = (long long)n_act * ((avg_rows + tiled - 1) / tiled) * (h->T2 / 4);
+        while (sk2 < 4 && wg * sk2 < 2048 && h->U2 / (sk2 * 2) >= 2) sk2 *= 2;
+        if (h->t_sk2 > 0) sk2 = h->t_sk2 < h->U2 ? h->t_sk2 : h->U2;
+        const size_t y_rows = h->arena->y_elems / h->H;
+        while (sk2 > 1 && (size_t)sk2 * n_slots > y_rows) --sk2;
+    }
+    *pl = Plan{};
+    pl->t1 = LaunchCfg{1, tiled / 16, 1, 1, tiled, 4, 2, 11};       // ("pf" 11 in the description = gemm_i8a8_kernel)
+    pl->t2 = LaunchCfg{1, tiled / 16, 1, sk2, tiled, 4, 2, 11};
+}
+
 static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   // M, n_slots: as handed over (incl. -1 slots)
     if (h->mx8) return pick_cfg_mx8(h, M, n_slots, pl);
+    if (h->i8a) return pick_cfg_i8a(h, M, n_slots, pl);
     // Measured on MI355X (profiles/r01_sweep_*): one 16-row tile per wave streams best (7168 waves x 64
     // threads for Mixtral GEMM1: 6.7 TB/s vs 6.4 TB/s at two tiles); two tiles only for sub-16-bit
     // weights, where the token operand dominates the load instructions.
@@ -1065,6 +1117,12 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
         rc = launch_quant_mxfp8_rows(st, x, il.x_ld, h->adt, M, h->H, a->xq, (unsigned char*)a->xqs, true);
         if (rc != LKM_OK) return rc;
     }
+    if (h->i8a) {  // per-token int8 quantisation of the token rows (once per token): rows of whole units + one fp32 scale per row
+        LKM_REQUIRE((size_t)M * kb1 * 128 <= a->xq_n && n_slots * kb2 * 128 <= a->aq_n && (size_t)M <= a->xqs_n && n_slots <= a->aqs_n,
+                    "int8 activation scratch too small");
+        rc = launch_quant_int8_rows(st, x, il.x_ld, h->adt, M, h->H, a->xq, a->xqs, true);
+        if (rc != LKM_OK) return rc;
+    }
     if (h->ps) {   // int4 fast mode: the activation-side term, one fp32 sum per (token, 128-k block)
         LKM_REQUIRE((size_t)M * kb1 <= a->xqs_n && n_slots * kb2 <= a->aqs_n, "int4 activation-sum scratch too small");
         rc = launch_rowsum128_rows(st, x, (int)il.x_ld, h->adt, M, h->H, a->xqs);
@@ -1138,11 +1196,11 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
     p1.U = h->U1;
     p1.Kreal = h->H;
     p1.n_real = h->I;
-    p1.x = (h->a8 || h->mx8) ? (const void*)a->xq : x;
-    p1.ldx = h->a8 ? h->H : (h->mx8 ? kb1 * 128 : (int)il.x_ld);
+    p1.x = (h->a8 || h->mx8 || h->i8a) ? (const void*)a->xq : x;
+    p1.ldx = h->a8 ? h->H : ((h->mx8 || h->i8a) ? kb1 * 128 : (int)il.x_ld);
     p1.xscale = a->xqs;
-    p1.ld_xscale = kb1;
-    p1.round_gemm1 = (h->a8 || h->mx8) ? 1 : 0;
+    p1.ld_xscale = h->i8a ? 1 : kb1;
+    p1.round_gemm1 = (h->a8 || h->mx8 || h->i8a) ? 1 : 0;
     p1.top_k = K;
     p1.rcp_top_k = 1.0f / (float)K;
     // The gated GEMM1 of the fp8 prefill kernel quantises its own output (the 1 x 128 groups of the W8A8 intermediate:
@@ -1232,10 +1290,15 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
         rc = launch_quant_mxfp8_rows(st, a->act, h->ld_act, h->adt, (int)n_slots, h->I, a->aq, (unsigned char*)a->aqs, true);
         if (rc != LKM_OK) return rc;
     }
-    p2.x = (h->a8 || h->mx8) ? (const void*)a->aq : a->act;
-    p2.ldx = h->mx8 ? kb2 * 128 : h->ld_act;
+    if (h->i8a) {  // the intermediate (rounded to the activation dtype by GEMM1) through the same quantiser, along I: its amax spans
+                   // every weight tile of a row, so this pass cannot live in GEMM1's epilogue
+        rc = launch_quant_int8_rows(st, a->act, h->ld_act, h->adt, (int)n_slots, h->I, a->aq, a->aqs, true);
+        if (rc != LKM_OK) return rc;
+    }
+    p2.x = (h->a8 || h->mx8 || h->i8a) ? (const void*)a->aq : a->act;
+    p2.ldx = (h->mx8 || h->i8a) ? kb2 * 128 : h->ld_act;
     p2.xscale = a->aqs;
-    p2.ld_xscale = kb2;
+    p2.ld_xscale = h->i8a ? 1 : kb2;
     p2.top_k = K;
     p2.rcp_top_k = 1.0f / (float)K;
     p2.counts = a->counts;
@@ -1337,7 +1400,7 @@ static size_t chunk_tokens(const LkmEngine* h, int K) {
         if (h->arena->xq_n / (size_t)h->H < chunk) chunk = h->arena->xq_n / (size_t)h->H;
         if (h->arena->aq_n / ((size_t)K * h->I) < chunk) chunk = h->arena->aq_n / ((size_t)K * h->I);
     }
-    if (h->mx8) {
+    if (h->mx8 || h->i8a) {
         const size_t kp1 = (size_t)ceil_div(h->H, 128) * 128, kp2 = (size_t)ceil_div(h->I, 128) * 128;
         if (h->arena->xq_n / kp1 < chunk) chunk = h->arena->xq_n / kp1;
         if (h->arena->aq_n / ((size_t)K * kp2) < chunk) chunk = h->arena->aq_n / ((size_t)K * kp2);
@@ -1346,6 +1409,10 @@ static size_t chunk_tokens(const LkmEngine* h, int K) {
         const size_t kb1 = ceil_div(h->H, 128), kb2 = ceil_div(h->I, 128);
         if (h->arena->xqs_n / kb1 < chunk) chunk = h->arena->xqs_n / kb1;
         if (h->arena->aqs_n / ((size_t)K * kb2) < chunk) chunk = h->arena->aqs_n / ((size_t)K * kb2);
+    }
+    if (h->i8a) {      // one fp32 scale per row
+        if (h->arena->xqs_n < chunk) chunk = h->arena->xqs_n;
+        if (h->arena->aqs_n / (size_t)K < chunk) chunk = h->arena->aqs_n / (size_t)K;
     }
     return chunk;
 }
@@ -1384,12 +1451,11 @@ static std::vector<LkmEngine::TunedPlan> tune_candidates(const LkmEngine* h, int
     cands.push_back({0, 0, 0, 0, 0.f, "default"});
     Plan pl;
     pick_cfg(h, M, (size_t)M * K, &pl);
-    if (h->mx8) {      // MXFP4 x MXFP8: one kernel family, the candidates are its other token-tile heights (pick_cfg_mx8 ignores "pf" / "pd")
-        static const char* const names[4] = {"32-row tiles (gemm_mxa8.h)", "64-row tiles (gemm_mxa8.h)", "128-row tiles (gemm_mxa8.h)", "256-row tiles (gemm_mxa8.h)"};
-        for (int i = 0, t = 32; i < 4; ++i, t *= 2)
+    if (h->mx8 || h->i8a) {      // one kernel family: the candidates are its other token-tile heights (pick_cfg_mx8 / _i8a ignore "pf" / "pd")
+        for (int t = 32; t <= 256; t *= 2)
             if (t != pl.t1.tiled && (t <= 64 || (size_t)M * K >= (size_t)t)) {
                 LkmEngine::TunedPlan c{0, t, 0, 0, 0.f, ""};
-                snprintf(c.what, sizeof(c.what), "%s", names[i]);
+                snprintf(c.what, sizeof(c.what), "%d-row tiles (%s)", t, h->mx8 ? "gemm_mxa8.h" : "gemm_i8a8.h");
                 cands.push_back(c);
             }
         return cands;
@@ -1671,6 +1737,15 @@ extern "C" int lkm_quant_mxfp8_rows(void* stream, const void* x, int32_t x_dtype
     return launch_quant_mxfp8_rows((hipStream_t)stream, x, ld_x, x_dtype, rows, cols, q, scales, false);
 }
 
+extern "C" int lkm_quant_int8_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
+                                   void* q, float* scales) {
+    LKM_REQUIRE(x && q && scales, "lkm_quant_int8_rows: null pointer");
+    LKM_REQUIRE(x_dtype == LKM_DT_BF16 || x_dtype == LKM_DT_F16, "lkm_quant_int8_rows: 16-bit activations only");
+    LKM_REQUIRE(rows >= 0 && cols > 0 && cols % 32 == 0 && cols <= 131072 && ld_x >= cols && ld_x % 8 == 0 && ld_x <= 0x7fffffffLL && ((uintptr_t)x & 15) == 0 && ((uintptr_t)q & 7) == 0,
+                "lkm_quant_int8_rows: rows=%d cols=%d ld=%lld (cols a multiple of 32 up to 131072, ld of 8, x 16-byte and q 8-byte aligned)", rows, cols, (long long)ld_x);
+    return launch_quant_int8_rows((hipStream_t)stream, x, ld_x, x_dtype, rows, cols, q, scales, false);
+}
+
 extern "C" int lkm_wna16_expand(void* stream, const void* qweight, const void* scales, const void* zeros, void* out,
                                 int64_t rows, int32_t K, int32_t group, int32_t weight_bits, int32_t out_dtype) {
     LKM_REQUIRE(qweight && scales && out, "lkm_wna16_expand: null pointer");
@@ -1755,7 +1830,7 @@ extern "C" int64_t lkm_weight_bytes(LkmHandle h) { return h ? h->weight_bytes : 
 extern "C" int lkm_describe(LkmHandle h, char* buf, int32_t buf_len) {
     LKM_REQUIRE(h && buf && buf_len > 0, "null argument");
     snprintf(buf, buf_len, "E=%d H=%d I=%d wf=%d%s adt=%d gated=%d T1_half=%d U1=%d T2=%d U2=%d | %s",
-             h->E, h->Hu, h->I, h->wf, h->zp ? " zp=1" : (h->mx8 ? " a8=mxfp8 (gemm_mxa8_kernel)" : ""), h->adt, (int)h->gated, h->T1_half, h->U1, h->T2, h->U2,
+             h->E, h->Hu, h->I, h->wf, h->zp ? " zp=1" : (h->mx8 ? " a8=mxfp8 (gemm_mxa8_kernel)" : (h->i8a ? " a8=int8 (gemm_i8a8_kernel)" : "")), h->adt, (int)h->gated, h->T1_half, h->U1, h->T2, h->U2,
              h->last_desc);
     return LKM_OK;
 }
@@ -1909,6 +1984,9 @@ static void expert_slabs(const LkmEngine* h, int expert, ExpertSlabs* s) {
     if (h->ps) {
         sb13 = t13 * 16 * 4;
         sb2 = t2 * 16 * 4;
+    } else if (h->i8a) {
+        sb13 = halves * h->T1_half * 16 * 4;
+        sb2 = (size_t)h->T2 * 16 * 4;
     } else if (h->zp || h->wf == LKM_W_INT8) {
         sb13 = t13 * 16 * h->spu * 4;
         sb2 = t2 * 16 * h->spu * 4;

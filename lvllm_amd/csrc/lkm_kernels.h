@@ -72,6 +72,10 @@ int launch_quant_fp8_rows(hipStream_t st, const void* src, int ld_src, int adt, 
 // (q [R][Kp], scales [R][Kp / 32], pad columns 0 with scale byte 127): the token image of gemm_mxa8_kernel
 int launch_quant_mxfp8_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst,
                             unsigned char* scales, bool pad);
+// per-token int8 rows (int8 x int8): q [R][K] (pad = true: rows padded to whole 128-k units with zero bytes, the token image of
+// gemm_i8a8_kernel), scales fp32 [R] = amax / 127
+int launch_quant_int8_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst, float* scales,
+                           bool pad);
 // int4 fast mode: sums[r][kb] = fp32 sum of the 128 elements of group kb of row r (16-bit rows, row stride ld_src)
 int launch_rowsum128_rows(hipStream_t st, const void* src, int ld_src, int adt, int R, int K, float* sums);
 int launch_combine(hipStream_t st, const void* y, int y_dt, int SK, size_t sk_stride,

@@ -334,7 +334,8 @@ int launch_repack_w(hipStream_t st, int wf, const void* src, void* dst, const Re
         hipLaunchKernelGGL(repack_w_kernel<LKM_W_F16>, grid, block, 0, st, (const uint8_t*)src, (u32x4*)dst, d);
         break;
     case LKM_W_FP8_E4M3:
-    case LKM_W_INT8:     // one byte per weight: the fp8 byte shuffle (d.a8 = 0)
+    case LKM_W_INT8:     // one byte per weight: the fp8 byte shuffle -- d.a8 = 0 for the weight-only decoder kernels, d.a8 = 1 for int8
+                         // activations (gemm_i8a8.h: the fp8 W8A8 image, signed bytes)
         hipLaunchKernelGGL(repack_w_kernel<LKM_W_FP8_E4M3>, grid, block, 0, st, (const uint8_t*)src, (u32x4*)dst, d);
         break;
     case LKM_W_INT4_B8:

@@ -42,7 +42,7 @@ def _act_name(activation: Any) -> str:
 class LkmQuant:
     """What the engine needs of a FusedMoEQuantConfig (fused_moe/config.py): the weight format, its scales and
     group / block shape.  `from_vllm` reads the same facts off the reference's object."""
-    fmt: str = "bf16"                    # bf16 | fp16 | int4 | fp8 | mxfp4 | nvfp4 | wna16 (native or expanded: _engine_for)
+    fmt: str = "bf16"                    # bf16 | fp16 | int4 | int8 | fp8 | mxfp4 | nvfp4 | wna16 (native or expanded: _engine_for)
     w1_scale: torch.Tensor | None = None
     w2_scale: torch.Tensor | None = None
     group_n: int = 0
@@ -50,7 +50,8 @@ class LkmQuant:
     w1_global_scale: torch.Tensor | None = None
     w2_global_scale: torch.Tensor | None = None
     fp8_mode: int = _clib.FP8_W8A16      # FP8_W8A8: activations quantised on the fly -- fp8: 1x128 (in-tree block-fp8);
-                                         # mxfp4: MXFP8, 1x32 E8M0 blocks (mxfp4_mxfp8_moe_quant_config)
+                                         # mxfp4: MXFP8, 1x32 E8M0 blocks (mxfp4_mxfp8_moe_quant_config); int8: per-token int8
+                                         # against fp32 per-channel weight scales (int8_w8a8_moe_quant_config)
     # fmt "wna16": weight-only integers the packed uint4b8 format cannot hold -- zero points and / or 8 bits
     # (fused_moe.py:207-276).  _engine_for hands them to the engine's own zero-point uint4 / uint8 formats where the shape
     # allows it; otherwise they are expanded once to T((q - zp) * s) by lkm_wna16_expand and the 16-bit engine runs on them.
@@ -68,6 +69,22 @@ class LkmQuant:
                 raise ValueError(f"fp8 experts: only 128x128 block scales are supported, got {block}")
             return LkmQuant("fp8", qc.w1_scale, qc.w2_scale, 128, 128,
                             fp8_mode=_clib.FP8_W8A8 if getattr(qc, "use_fp8_w8a8", False) else _clib.FP8_W8A16)
+        if getattr(qc, "use_int8_w8a8", False):
+            # int8 weights x int8 activations (config.py:650-673).  The engine has ONE such scheme: dynamic per-token activation
+            # scales against one static scale per weight row (gemm_i8a8_kernel); every other shape of the scales is refused by name
+            missing = []
+            if block is not None:
+                missing.append(f"block-quantised int8 (block_shape {list(block)})")
+            if not getattr(qc, "per_act_token_quant", False):
+                missing.append("per-tensor activation scales (per_act_token_quant=False)")
+            if getattr(qc, "a1_scale", None) is not None or getattr(qc, "a2_scale", None) is not None:
+                missing.append("static activation scales (a1_scale / a2_scale)")
+            missing += [name for name in ("w1_bias", "w2_bias") if getattr(qc, name, None) is not None]
+            if missing:
+                raise ValueError("int8 W8A8 experts: the MI355X engine runs dynamic per-token int8 activations against "
+                                 "per-channel weight scales only; not supported: " + ", ".join(missing))
+            # group_k = the whole K of either GEMM: 131072, the largest K the int32 sums allow (include/lkm.h)
+            return LkmQuant("int8", qc.w1_scale, qc.w2_scale, 1, 1 << 17, fp8_mode=_clib.FP8_W8A8)
         int4, int8 = getattr(qc, "use_int4_w4a16", False), getattr(qc, "use_int8_w8a16", False)
         if int4 or int8:
             for name in ("w1_bias", "w2_bias"):
@@ -94,6 +111,11 @@ class LkmQuant:
                     raise ValueError(f"MXFP4 x MXFP8 experts with {name} are not supported by the MI355X engine")
             return LkmQuant("mxfp4", qc.w1_scale, qc.w2_scale, 1, 32, fp8_mode=_clib.FP8_W8A8)
         raise ValueError("quantisation scheme of this FusedMoEQuantConfig is not supported by the MI355X engine")
+
+
+def _is_i8(key_text: str) -> bool:
+    """a lower-cased QuantKey text that names signed int8 ("i8" as the reference prints torch.int8, or "int8" spelt out)"""
+    return "uint8" not in key_text and ("int8" in key_text or "(i8," in key_text)
 
 
 def _unpack_zp4(zp: torch.Tensor) -> torch.Tensor:
@@ -179,11 +201,16 @@ class LkmExperts:
             return a == "none" or "mxfp8" in a              # W4A16, or MXFP8 activations on the scaled MFMA (W4A8)
         if "nvfp4" in w:
             return a == "none"                              # W4A16
+        if _is_i8(w) and _is_i8(a):
+            # Integer ACTIVATIONS (w8a8 int8) in ONE shape: int8 with a static per-channel scale x int8 with a dynamic
+            # per-token scale (kInt8StaticChannelSym x kInt8DynamicTokenSym, printed QuantKey(i8,scale(f32,static,per_channel),
+            # symmetric) / QuantKey(i8,scale(f32,dynamic,per_token),symmetric)) on the integer MFMA.  A pair that names no scale
+            # shape (the bare "int8"), block and per-tensor int8 are not supported.
+            return "static" in w and "per_channel" in w and "dynamic" in a and "per_token" in a
         if "int4" in w or "uint4" in w or "int8" in w or "uint8" in w:
             # uint4b8 and zero-point uint4 natively, 8-bit weight-only (uint8b128 / uint8 + zp) natively with
             # LKM_WNA16_EXPAND=0; otherwise, and for shapes outside the engine's group rule, expanded to 16 bits at
-            # hand-off (LkmQuant fmt "wna16", _engine_for).  Integer
-            # ACTIVATIONS (w8a8 int8) are not supported.
+            # hand-off (LkmQuant fmt "wna16", _engine_for).
             return a == "none"
         return False
 

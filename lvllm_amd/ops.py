@@ -281,6 +281,19 @@ def quant_mxfp8_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q, sc
 
 
+def quant_int8_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [rows, cols] bf16 / fp16 (cols a multiple of 32, row stride of 8) -> (q int8 [rows, cols], scales fp32 [rows]): the
+    dynamic per-token quantiser (scale = amax / 127, q = rint(x * (127 / amax)), ties to even) the int8 x int8 engines run on
+    their inputs."""
+    _need_cuda(x)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.bfloat16, torch.float16)
+    rows, cols = x.shape
+    q = torch.empty((rows, cols), dtype=torch.int8, device=x.device)
+    sc = torch.empty((rows,), dtype=torch.float32, device=x.device)
+    _clib.check(_clib.lib().lkm_quant_int8_rows(_stream(x), _ptr(x), _DT[x.dtype], x.stride(0), rows, cols, _ptr(q), _ptr(sc)))
+    return q, sc
+
+
 def wna16_expand(qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor | None, weight_bits: int,
                  group: int) -> torch.Tensor:
     """Weight-only integer experts -> 16-bit weights T((q - zp) * s), the in-tree operator's dequantisation
@@ -452,7 +465,12 @@ class RoutedExpertsEngine:
         takes them the same way, one byte 0..255 each, both or neither: without them the layer is symmetric uint8b128.
         fp8_mode with fmt "mxfp4": FP8_W8A16 (0) keeps the weight-only path; FP8_W8A8 quantises the hidden states and the
         intermediate to MXFP8 (1 x 32 E8M0 blocks, lkm_quant_mxfp8_rows) and runs both GEMMs on the scaled MFMA
-        (gemm_mxa8_kernel: W4A8, the reference's mxfp4_mxfp8_moe_quant_config)."""
+        (gemm_mxa8_kernel: W4A8, the reference's mxfp4_mxfp8_moe_quant_config).
+        fp8_mode with fmt "int8": FP8_W8A16 (0) keeps the weight-only path; FP8_W8A8 is W8A8-int8 (the reference's
+        int8_w8a8_moe_quant_config with per_act_token_quant): w13 / w2 are torch.int8 [E, rows, K], the scales fp32 [E, rows]
+        (or [E, rows, 1]), one per weight row -- group_n = 1, group_k >= max(hidden, intermediate) -- and there are no zero
+        points; the hidden states and the intermediate are quantised per token (lkm_quant_int8_rows) and both GEMMs run
+        on the integer MFMA (gemm_i8a8_kernel)."""
         E = w13.shape[0]
         H = w2.shape[1]
         inter = w13.shape[1] // (2 if has_gate_proj else 1)
@@ -481,6 +499,14 @@ class RoutedExpertsEngine:
         elif int4_mode == _clib.INT4_ZP:
             raise ValueError("int4_mode ZP without zero points")
         cfg.int4_mode = int4_mode
+        if fmt == "int8" and fp8_mode == _clib.FP8_W8A8:
+            if w13_zp is not None:
+                raise ValueError("int8 experts with int8 activations (fp8_mode=1) are symmetric: no zero points")
+            if w13.dtype != torch.int8 or w2.dtype != torch.int8:
+                raise ValueError(f"int8 experts with int8 activations take torch.int8 weights, got {w13.dtype} / {w2.dtype}")
+            if w13_scale is None or w2_scale is None or w13_scale.dtype != torch.float32 or w2_scale.dtype != torch.float32 \
+                    or w13_scale.numel() != E * w13.shape[1] or w2_scale.numel() != E * H:
+                raise ValueError("int8 experts with int8 activations take fp32 scales [E, rows] (or [E, rows, 1]), one per weight row")
         self.cfg = cfg
         self.H, self.K, self.act_dtype = H, top_k, act_dtype
         cls = _CLS[(fmt, act_dtype)]
