@@ -46,7 +46,8 @@ extern "C" {
 #define LKM_W_NVFP4 4    /* MOE_NVFP4[_FP16]  : E2M1 bytes [E,N,K/2] + fp8 e4m3fn block scales       *
                           *   [E,N,K/16] (linear) + per-expert f32 multipliers [E] (global)  */
 #define LKM_W_MXFP4 5    /* MOE_MXFP4[_FP16]  : E2M1 bytes [E,N,K/2] + uint8 E8M0 scales [E,N,K/32]; fp8_mode 0 = weight-only *
-                          *   (W4A16), LKM_FP8_W8A8 = MXFP8 activations on the scaled MFMA (W4A8, see LKM_FP8_* below)         */
+                          *   (W4A16), LKM_FP8_W8A8 = MXFP8 activations (W4A8), LKM_FP8_MXA4 = MXFP4 activations (W4A4), both on  *
+                          *   the scaled MFMA (see LKM_FP8_* below)                                                             */
 #define LKM_W_INT8 6     /* weight-only 8 bits (the in-tree operator's int8_w8a16, fused_moe.py:207-276; no lk_moe class): *
                           *   uint8 bytes [E,N,K] + act-dtype scales [E,N,K/group] (groupN == 1, the group rule of         *
                           *   LKM_W_INT4_B8), dequantised to T((q - zp) * s).  Zero points: uint8 [E,N,K/group] in the two  *
@@ -63,11 +64,14 @@ extern "C" {
 /* fp8 compute mode */
 #define LKM_FP8_W8A16 0 /* lk_moe semantics: weight-only fp8, activations stay bf16/fp16      */
 #define LKM_FP8_W8A8 1  /* in-tree operator semantics: dynamic 1 x groupK activation quant     */
+#define LKM_FP8_MXA4 4  /* LKM_W_MXFP4 only: MXFP4 activations (4 = the activation's bits)       */
 /* With weight_format LKM_W_MXFP4 the field selects the activation side of the MX product: 0 keeps the weight-only path
  * (16-bit activations), LKM_FP8_W8A8 quantises the hidden states and the intermediate to MXFP8 (1 x 32 blocks: one E8M0
  * byte + 32 e4m3fn bytes, lkm_quant_mxfp8_rows) and both GEMMs run on v_mfma_scale_f32_16x16x128_f8f6f4 with the
- * E8M0 scales of both operands applied by the instruction (the reference's mxfp4_mxfp8_moe_quant_config).  Any other
- * value is LKM_E_INVALID.
+ * E8M0 scales of both operands applied by the instruction (the reference's mxfp4_mxfp8_moe_quant_config); LKM_FP8_MXA4
+ * quantises them to MXFP4 instead (one E8M0 byte + 32 E2M1 nibbles, lkm_quant_mxfp4_rows) and both operands of the
+ * instruction are fp4 (the reference's mxfp4_moe_quant_config / use_mxfp4_w4a4, quark's w_mxfp4_a_mxfp4).  Any other
+ * value (2 and 3 included) is LKM_E_INVALID.
  * With weight_format LKM_W_INT8 it selects integer activations: 0 keeps the weight-only path, LKM_FP8_W8A8 quantises the
  * hidden states and the intermediate per token to int8 (scale = amax / 127, lkm_quant_int8_rows) and both GEMMs run on
  * v_mfma_i32_16x16x64_i8 with exact int32 sums; the token scale and the weight row's scale meet the sum once, in the
@@ -318,6 +322,17 @@ int lkm_quant_mxfp8_rows(void* stream, const void* x, int32_t x_dtype, int64_t l
  * LKM_FP8_W8A8 layer; exposed so that the bytes can be checked. */
 int lkm_quant_int8_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
                         void* q, float* scales);
+
+/* MXFP4 quantisation of activation rows (the dynamic quantiser of the reference's mxfp4_moe_quant_config, rounding "even"):
+ * per 32 columns one E8M0 byte + 32 E2M1 values.  x [rows][ld_x] 16-bit (x_dtype), cols % 32 == 0; q [rows][cols / 2] bytes,
+ * two values per byte, the even column in the low nibble (the weights' convention); scales uint8 [rows][cols / 32] row-major.
+ * In fp32: b = (bits(amax) + 0x200000) & 0xFF800000 (amax rounded up to the next power of two when its mantissa is >= 1.75),
+ * byte = clamp((b >> 23) - 2, 0, 254); amax = 0 gives byte 0 and zero values; values = e2m1(x * 2^(127 - byte)), round to
+ * nearest on {0, .5, 1, 1.5, 2, 3, 4, 6} with ties to the even code, magnitudes above 6 saturate, the sign is kept.  NaN / Inf
+ * inputs are unspecified.  The engine runs the same kernel on the inputs of an LKM_W_MXFP4 / LKM_FP8_MXA4 layer; exposed so
+ * that the bytes can be checked. */
+int lkm_quant_mxfp4_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
+                         void* q, uint8_t* scales);
 
 /*
  * Weight-only integer experts of the in-tree operator surface (secondary boundary): int4_w4a16 / int8_w8a16 with or

@@ -20,6 +20,7 @@ DT_F32, DT_BF16, DT_F16 = 0, 1, 2
 W_BF16, W_F16, W_FP8_E4M3, W_INT4_B8, W_NVFP4, W_MXFP4, W_INT8 = 0, 1, 2, 3, 4, 5, 6
 ACT_SILU, ACT_SWIGLUOAI, ACT_RELU2 = 0, 1, 2
 FP8_W8A16, FP8_W8A8 = 0, 1
+FP8_MXA4 = 4            # W_MXFP4 only: MXFP4 activations (include/lkm.h LKM_FP8_MXA4)
 INT4_EXACT, INT4_FAST, INT4_ZP = 0, 1, 2
 PROF_SORT, PROF_GEMM1, PROF_GEMM2, PROF_COMBINE, PROF_N = 0, 1, 2, 3, 4
 
@@ -81,6 +82,8 @@ _SIGS = {
     "lkm_per_token_group_quant_fp8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                               C.c_void_p, C.c_void_p]),
     "lkm_quant_mxfp8_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_void_p]),
+    "lkm_quant_mxfp4_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                      C.c_void_p, C.c_void_p]),
     "lkm_quant_int8_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
                                     C.c_void_p, C.c_void_p]),

@@ -955,6 +955,88 @@ int launch_quant_int8_rows(hipStream_t st, const void* src, long long ld_src, in
     return LKM_OK;
 }
 
+// ------------------------------------------------------------------ MXFP4 activation rows (MXFP4 x MXFP4, gemm_mxa4.h)
+// Per row and 32 consecutive columns: one E8M0 byte + 32 E2M1 nibbles (two per byte, even column in the low nibble: the weights'
+// convention).  The work split is the MXFP8 quantiser's: one lane owns an aligned 8-column piece (one 16-byte load, one 4-byte
+// store), the four lanes of a block reduce the integer maximum of the magnitude bits with two quad-permute DPP moves.
+//   b = (bits(amax) + 0x200000) & 0xFF800000       amax rounded up to the next power of two when its mantissa is >= 1.75
+//   byte = clamp((b >> 23) - 2, 0, 254)            (6 = 1.5 * 2^2 is the largest E2M1 magnitude); amax = 0 -> byte 0, values 0
+//   q = e2m1(x * 2^(127 - byte))                   v_ldexp_f32: exact; what underflows there is far below the first tie (0.25)
+// E2M1 rounding in VALU, round to nearest with ties to the even code, magnitudes above 6 saturate: the grid's step is 0.5 below 2,
+// 1 below 4 and 2 above, so adding and subtracting 2^22 / 2^23 / 2^24 (whose fp32 ulp is that step, RNE) rounds onto the grid, and
+// the sum's even mantissa IS the even code (.25 -> 0, .75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4).
+// PAD = false: the plain row-major form of lkm_quant_mxfp4_rows (q [R][K / 2], scales [R][K / 32]).  PAD = true: the engine's
+// image -- rows padded to whole 256-k stages of gemm_mxa4_kernel, q [R][S * 128], scales [R][S] pairs of dwords whose eight
+// bytes are ordered [32-block of the unit g][unit of the stage h] (the two scales of an MFMA lane are one 16-bit word); pad
+// columns are value 0 with scale byte 127.
+__device__ __forceinline__ unsigned e2m1_rne(float v) {
+    const float a = __builtin_fminf(__builtin_fabsf(v), 6.0f);
+    const float magic = a < 2.0f ? 4194304.0f : (a < 4.0f ? 8388608.0f : 16777216.0f);
+    const float r = (a + magic) - magic;                         // on the grid {0, .5, 1, 1.5, 2, 3, 4, 6}
+    const int code = r < 2.0f ? (int)(r * 2.0f) : (r < 4.0f ? (int)r + 2 : (int)(r * 0.5f) + 4);
+    return (unsigned)code | ((__builtin_bit_cast(unsigned, v) >> 28) & 8u);
+}
+
+template <int ADT, bool PAD>
+__global__ __launch_bounds__(256) void quant_mxfp4_rows_kernel(const unsigned short* __restrict__ src, long long ld_src, int R,
+                                                               int K, unsigned char* __restrict__ dst,
+                                                               unsigned char* __restrict__ scales) {
+    const int Kp = PAD ? (K + 255) / 256 * 256 : K;
+    const int PPR = Kp >> 3;                                     // 8-column pieces per row (K % 32 == 0)
+    const long long pc = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (pc >= (long long)R * PPR) return;                        // (PPR % 4 == 0: the four lanes of a block leave together)
+    const int row = (int)(pc / PPR), k = (int)(pc % PPR) * 8;
+    const bool in = k < K;                                       // a 32-block is wholly inside or wholly pad
+    u32x4 raw = {0u, 0u, 0u, 0u};
+    if (in) raw = *(const u32x4*)(src + (size_t)row * ld_src + k);
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = ActT<ADT>::to_f32((unsigned short)(raw[i] & 0xffffu));
+        v[2 * i + 1] = ActT<ADT>::to_f32((unsigned short)(raw[i] >> 16));
+    }
+    int amax = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int b = __builtin_bit_cast(int, v[i]) & 0x7fffffff;
+        amax = b > amax ? b : amax;
+    }
+    {
+        int o = __builtin_amdgcn_update_dpp(0, amax, 0xB1, 0xf, 0xf, true);      // quad_perm [1,0,3,2]
+        amax = o > amax ? o : amax;
+        o = __builtin_amdgcn_update_dpp(0, amax, 0x4E, 0xf, 0xf, true);          // quad_perm [2,3,0,1]
+        amax = o > amax ? o : amax;
+    }
+    int byte = 127;
+    if (in) {
+        byte = (int)(((unsigned)amax + 0x200000u) >> 23) - 2;
+        byte = byte < 0 ? 0 : (byte > 254 ? 254 : byte);
+    }
+    unsigned o = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) o |= e2m1_rne(__builtin_ldexpf(v[i], 127 - byte)) << (4 * i);
+    *(unsigned*)(dst + (size_t)row * (Kp >> 1) + (k >> 1)) = o;
+    if ((k & 31) == 0) {
+        const int blk = k >> 5;                                  // PAD: stage blk / 8, unit (blk >> 2) & 1, block of the unit blk & 3
+        const int at = PAD ? (blk & ~7) + (blk & 3) * 2 + ((blk >> 2) & 1) : blk;
+        scales[(size_t)row * (Kp >> 5) + at] = (unsigned char)byte;
+    }
+}
+
+int launch_quant_mxfp4_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst,
+                            unsigned char* scales, bool pad) {
+    if (R <= 0) return LKM_OK;
+    const int Kp = pad ? (K + 255) / 256 * 256 : K;
+    const long long pieces = (long long)R * (Kp >> 3);
+    dim3 grid((unsigned)((pieces + 255) / 256)), block(256);
+#define LKM_MXQ(ADT_, PAD_) hipLaunchKernelGGL((quant_mxfp4_rows_kernel<ADT_, PAD_>), grid, block, 0, st, (const unsigned short*)src, ld_src, R, K, (unsigned char*)dst, scales)
+    if (adt == LKM_DT_BF16) { if (pad) LKM_MXQ(LKM_DT_BF16, true); else LKM_MXQ(LKM_DT_BF16, false); }
+    else { if (pad) LKM_MXQ(LKM_DT_F16, true); else LKM_MXQ(LKM_DT_F16, false); }
+#undef LKM_MXQ
+    LKM_HIP_CHECK(hipGetLastError());
+    return LKM_OK;
+}
+
 // ------------------------------------------------------------------ 128-element row sums (int4 fast mode)
 // sums[row][kb] = sum of x[row][kb*128 .. +127] in fp32: the activation-side term of
 //   sum_k s (v_k - 8) x_k = s (sum_k (BIAS + v_k) x_k - (BIAS + 8) sum_k x_k)      (lkm_common.h LKM_W_INT4_PS).

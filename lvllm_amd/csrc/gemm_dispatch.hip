@@ -27,6 +27,11 @@ int launch_gemm1_tiled_mxa8_bf16(hipStream_t, const LaunchCfg&, const GemmParams
 int launch_gemm2_tiled_mxa8_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
 int launch_gemm1_tiled_mxa8_f16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
 int launch_gemm2_tiled_mxa8_f16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
+// MXFP4 x MXFP4 on the scaled MFMA, both operands fp4 (gemm_mxa4.h): likewise one family of tile kernels
+int launch_gemm1_tiled_mxa4_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
+int launch_gemm2_tiled_mxa4_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
+int launch_gemm1_tiled_mxa4_f16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
+int launch_gemm2_tiled_mxa4_f16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
 // int8 x per-token int8 on the integer MFMA (gemm_i8a8.h): likewise one family of tile kernels
 int launch_gemm1_tiled_i8a8_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, bool, int);
 int launch_gemm2_tiled_i8a8_bf16(hipStream_t, const LaunchCfg&, const GemmParams&, int);
@@ -136,6 +141,7 @@ int launch_gemm1_tiled(hipStream_t st, int wf, int adt, const LaunchCfg& cfg, co
         if (launch_w4x(st, wf, adt, cfg, p, gated, true, max_tiles, &rc)) return rc;
     }
     if (wf == LKM_W_MXFP4_A8) return adt == LKM_DT_BF16 ? launch_gemm1_tiled_mxa8_bf16(st, cfg, p, gated, max_tiles) : launch_gemm1_tiled_mxa8_f16(st, cfg, p, gated, max_tiles);
+    if (wf == LKM_W_MXFP4_A4) return adt == LKM_DT_BF16 ? launch_gemm1_tiled_mxa4_bf16(st, cfg, p, gated, max_tiles) : launch_gemm1_tiled_mxa4_f16(st, cfg, p, gated, max_tiles);
     if (wf == LKM_W_INT8_A8) return adt == LKM_DT_BF16 ? launch_gemm1_tiled_i8a8_bf16(st, cfg, p, gated, max_tiles) : launch_gemm1_tiled_i8a8_f16(st, cfg, p, gated, max_tiles);
     if (wf == LKM_W_BF16 && adt == LKM_DT_BF16) return launch_gemm1_tiled_bf16(st, cfg, p, gated, max_tiles);
     if (wf == LKM_W_F16 && adt == LKM_DT_F16) return launch_gemm1_tiled_f16(st, cfg, p, gated, max_tiles);
@@ -167,6 +173,7 @@ int launch_gemm2_tiled(hipStream_t st, int wf, int adt, const LaunchCfg& cfg, co
         if (launch_w4x(st, wf, adt, cfg, p, false, false, max_tiles, &rc)) return rc;
     }
     if (wf == LKM_W_MXFP4_A8) return adt == LKM_DT_BF16 ? launch_gemm2_tiled_mxa8_bf16(st, cfg, p, max_tiles) : launch_gemm2_tiled_mxa8_f16(st, cfg, p, max_tiles);
+    if (wf == LKM_W_MXFP4_A4) return adt == LKM_DT_BF16 ? launch_gemm2_tiled_mxa4_bf16(st, cfg, p, max_tiles) : launch_gemm2_tiled_mxa4_f16(st, cfg, p, max_tiles);
     if (wf == LKM_W_INT8_A8) return adt == LKM_DT_BF16 ? launch_gemm2_tiled_i8a8_bf16(st, cfg, p, max_tiles) : launch_gemm2_tiled_i8a8_f16(st, cfg, p, max_tiles);
     if (wf == LKM_W_BF16 && adt == LKM_DT_BF16) return launch_gemm2_tiled_bf16(st, cfg, p, max_tiles);
     if (wf == LKM_W_F16 && adt == LKM_DT_F16) return launch_gemm2_tiled_f16(st, cfg, p, max_tiles);

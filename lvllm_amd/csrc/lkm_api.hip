@@ -170,6 +170,8 @@ struct LkmEngine {
     bool a8;
     bool mx8;                  // MXFP4 weights x MXFP8 activations (fp8_mode W8A8 with LKM_W_MXFP4): kernel format LKM_W_MXFP4_A8, its own
                                // weight / scale image, both GEMMs on gemm_mxa8_kernel (every step size is one of its tile heights)
+    bool mx4;                  // MXFP4 weights x MXFP4 activations (fp8_mode LKM_FP8_MXA4): kernel format LKM_W_MXFP4_A4, the weight / scale
+                               // images of mx8, both GEMMs on gemm_mxa4_kernel (tokens: 64 B per unit in rows of whole 256-k stages)
     bool i8a;                  // int8 weights x per-token int8 activations (fp8_mode W8A8 with LKM_W_INT8): kernel format LKM_W_INT8_A8, the fp8
                                // W8A8 weight image + one fp32 scale per weight row, both GEMMs on gemm_i8a8_kernel
     bool zp;                   // uint4 with zero points (int4_mode ZP): (scale, zero point) pairs in the scale image, kernel format LKM_W_INT4_ZP
@@ -378,7 +380,8 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         LKM_REQUIRE(cfg->groupK == g && cfg->groupN == 1, "lkm_create: %s block scales are 1 x %d (got groupN=%d groupK=%d)", wf == LKM_W_MXFP4 ? "MXFP4" : "NVFP4", g, cfg->groupN, cfg->groupK);
         LKM_REQUIRE(cfg->hidden_size % 32 == 0 && cfg->intermediate_size % 32 == 0, "lkm_create: fp4 formats need hidden and intermediate sizes that are multiples of 32");
         // MXFP4: fp8_mode selects the activation side -- 0 weight-only (16-bit activations), W8A8 = MXFP8 activations (include/lkm.h)
-        LKM_REQUIRE(wf != LKM_W_MXFP4 || cfg->fp8_mode == 0 || cfg->fp8_mode == LKM_FP8_W8A8, "lkm_create: bad fp8_mode %d for MXFP4 (0 = weight-only, %d = MXFP8 activations)", cfg->fp8_mode, LKM_FP8_W8A8);
+        LKM_REQUIRE(wf != LKM_W_MXFP4 || cfg->fp8_mode == 0 || cfg->fp8_mode == LKM_FP8_W8A8 || cfg->fp8_mode == LKM_FP8_MXA4,
+                    "lkm_create: bad fp8_mode %d for MXFP4 (0 = weight-only, %d = MXFP8 activations, %d = MXFP4 activations)", cfg->fp8_mode, LKM_FP8_W8A8, LKM_FP8_MXA4);
     }
     const bool i8a = wf == LKM_W_INT8 && cfg->fp8_mode == LKM_FP8_W8A8;
     if (wf == LKM_W_INT8) LKM_REQUIRE(cfg->fp8_mode == 0 || i8a, "lkm_create: bad fp8_mode %d for int8 (0 = weight-only, %d = per-token int8 activations)", cfg->fp8_mode, LKM_FP8_W8A8);
@@ -436,8 +439,9 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
     h->ps = wf == LKM_W_INT4_B8 && cfg->int4_mode == LKM_INT4_FAST;
     h->zp = wf == LKM_W_INT4_B8 && cfg->int4_mode == LKM_INT4_ZP;
     h->mx8 = wf == LKM_W_MXFP4 && cfg->fp8_mode == LKM_FP8_W8A8;
+    h->mx4 = wf == LKM_W_MXFP4 && cfg->fp8_mode == LKM_FP8_MXA4;
     h->i8a = i8a;
-    h->wfk = h->a8 ? LKM_W_FP8_A8 : (h->ps ? LKM_W_INT4_PS : (h->zp ? LKM_W_INT4_ZP : (h->mx8 ? LKM_W_MXFP4_A8 : (i8a ? LKM_W_INT8_A8 : wf))));
+    h->wfk = h->a8 ? LKM_W_FP8_A8 : (h->ps ? LKM_W_INT4_PS : (h->zp ? LKM_W_INT4_ZP : (h->mx8 ? LKM_W_MXFP4_A8 : (h->mx4 ? LKM_W_MXFP4_A4 : (i8a ? LKM_W_INT8_A8 : wf)))));
     h->unitk = wf_unitk(wf);
     h->T1_half = round_up(ceil_div(h->I, 16), 4);
     h->U1 = ceil_div(h->H, h->unitk);
@@ -501,7 +505,7 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         }
         return r;
     };
-    const int wfr = h->ps ? LKM_W_INT4_PS : (h->mx8 ? LKM_W_MXFP4_A8 : wf);
+    const int wfr = h->ps ? LKM_W_INT4_PS : ((h->mx8 || h->mx4) ? LKM_W_MXFP4_A8 : wf);      // (W4A4 reuses the W4A8 images)
     {
         const size_t b13 = (size_t)halves * h->I * h->Hu * wbytes_per_elem_x2(wf) / 2;    // source bytes per expert
         const size_t b2 = (size_t)h->Hu * h->I * wbytes_per_elem_x2(wf) / 2;
@@ -556,7 +560,7 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
         auto rs2 = [&](const void* sp, void* dp, const RepackDims& dd) { return launch_repack_s_int4(nullptr, sp, dp, dd, gk2, h->spu); };
         LKM_TRY(hand_off(w13_scale, (size_t)halves * h->I * (h->H / gk13) * 2, h->s13, n13 * 2, d13, rs13));
         LKM_TRY(hand_off(w2_scale, (size_t)h->H * (h->I / gk2) * 2, h->s2, n2 * 2, d2, rs2));
-    } else if (h->mx8) {       // one E8M0 byte per (row, 32-block) as [tile][ceil(U / 4)][lane] dwords: 1/32 B per weight (+ the unit padding)
+    } else if (h->mx8 || h->mx4) {       // one E8M0 byte per (row, 32-block) as [tile][ceil(U / 4)][lane] dwords: 1/32 B per weight (+ the unit padding)
         const size_t n13 = (size_t)halves * h->T1_half * ceil_div(h->U1, 4) * 256, n2 = (size_t)h->T2 * ceil_div(h->U2, 4) * 256;
         LKM_TRY_HIP(hipMalloc(&h->s13, h->E * n13));
         LKM_TRY_HIP(hipMalloc(&h->s2, h->E * n2));
@@ -607,15 +611,18 @@ extern "C" int lkm_create(const LkmConfig* cfg, const void* w13, const void* w2,
     const size_t y_rows = slots > 8 * (slots < 2048 ? slots : 2048) ? slots : 8 * (slots < 2048 ? slots : 2048);
     {
         const size_t kb1 = ceil_div(h->H, 128), kb2 = ceil_div(h->I, 128);
-        const bool xs = h->a8 || h->ps || h->mx8;       // per-(row, 128-k) scalars: activation scales / activation sums / (MXFP8) one
+        const bool xs = h->a8 || h->ps || h->mx8 || h->mx4;       // per-(row, 128-k) scalars: activation scales / activation sums / (MXFP8) one
                                                         // dword of four E8M0 bytes -- the same four bytes per row and unit
         const bool q8 = h->mx8 || i8a;                  // 8-bit activation rows padded to whole units (int8: + ONE fp32 scale per row)
+        // MXFP4 activations: rows of whole 256-k stages, 128 value bytes + one scale dword pair per stage (gemm_mxa4.h)
+        const size_t st1 = ceil_div(h->H, 256), st2 = ceil_div(h->I, 256);
         // the fp8 x fp8 prefill kernel's item lists: (256-row token tiles of the largest chunk) x (row groups of GEMM1 + GEMM2)
         const size_t items_n = h->a8 ? (slots / 256 + (size_t)h->E + 8) * (size_t)(a8w_row_groups(h, 1) + a8w_row_groups(h, 2)) * 4 : 0;
         LKM_TRY(arena_reserve(h->device, h->E, slots, slots * h->ld_act, y_rows * h->H,
-                              h->a8 ? cap * h->H : (q8 ? cap * kb1 * 128 : 0), xs ? cap * kb1 : (i8a ? cap : 0),
-                              h->a8 ? slots * h->I : (q8 ? slots * kb2 * 128 : 0),
-                              xs ? slots * kb2 : (i8a ? slots : 0), items_n, &h->arena));
+                              h->a8 ? cap * h->H : (q8 ? cap * kb1 * 128 : (h->mx4 ? cap * st1 * 128 : 0)),
+                              h->mx4 ? cap * st1 * 2 : (xs ? cap * kb1 : (i8a ? cap : 0)),
+                              h->a8 ? slots * h->I : (q8 ? slots * kb2 * 128 : (h->mx4 ? slots * st2 * 128 : 0)),
+                              h->mx4 ? slots * st2 * 2 : (xs ? slots * kb2 : (i8a ? slots : 0)), items_n, &h->arena));
     }
     if (h->Hu != h->H) {       // aligned scratch rows for the token and output matrices of one chunk
         LKM_TRY_HIP(hipMalloc(&h->pad_x, cap * (size_t)h->H * 2));
@@ -644,11 +651,12 @@ struct Plan {
     LaunchCfg b1, b2;
 };
 
-// MXFP4 x MXFP8: one kernel family (gemm_mxa8.h), the plan is its token-tile height and GEMM2's split-K.  The streamer, the
+// MXFP4 x MXFP8 and MXFP4 x MXFP4: one kernel family each (gemm_mxa8.h / gemm_mxa4.h), the plan is its token-tile height and GEMM2's split-K.  The streamer, the
 // hybrid, the direct decode path, the 32x32-MFMA kernels and gemm_prefill.h have no kernel for the format: "tiled" < 0 and
 // every "pf" are ignored (as the fp8 W8A8 mode ignores the 4-bit "pf" values), a forced height is rounded to the next built one.
 // Thresholds: the 4-bit tile rules (32 rows while an expert is unlikely to hold more, 64, 128 from 64 rows per expert) and
-// the fp8 x fp8 rule for the prefill height (192 rows per expert).
+// the fp8 x fp8 rule for the prefill height (192 rows per expert).  The MXFP4 x MXFP4 family starts from the same thresholds
+// (DESIGN.md section 4 says what was re-measured).
 static void pick_cfg_mx8(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {
     const size_t n_eff = h->t_valid_den > 1 ? (n_slots + h->t_valid_den - 1) / h->t_valid_den : n_slots;
     const int n_act = (int)((size_t)h->E < n_eff ? (size_t)h->E : n_eff);
@@ -669,8 +677,9 @@ static void pick_cfg_mx8(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {
         while (sk2 > 1 && (size_t)sk2 * n_slots > y_rows) --sk2;
     }
     *pl = Plan{};
-    pl->t1 = LaunchCfg{1, tiled / 16, 1, 1, tiled, 4, 2, 10};       // ("pf" 10 in the description = gemm_mxa8_kernel)
-    pl->t2 = LaunchCfg{1, tiled / 16, 1, sk2, tiled, 4, 2, 10};
+    const int pf = h->mx4 ? 12 : 10;                                // ("pf" 10 in the description = gemm_mxa8_kernel, 12 = gemm_mxa4_kernel)
+    pl->t1 = LaunchCfg{1, tiled / 16, 1, 1, tiled, 4, 2, pf};
+    pl->t2 = LaunchCfg{1, tiled / 16, 1, sk2, tiled, 4, 2, pf};
 }
 
 // int8 x per-token int8: likewise one kernel family (gemm_i8a8.h) -- a token-tile height by rows per expert and GEMM2's split-K in
@@ -699,7 +708,7 @@ static void pick_cfg_i8a(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {
 }
 
 static void pick_cfg(const LkmEngine* h, int M, size_t n_slots, Plan* pl) {   // M, n_slots: as handed over (incl. -1 slots)
-    if (h->mx8) return pick_cfg_mx8(h, M, n_slots, pl);
+    if (h->mx8 || h->mx4) return pick_cfg_mx8(h, M, n_slots, pl);
     if (h->i8a) return pick_cfg_i8a(h, M, n_slots, pl);
     // Measured on MI355X (profiles/r01_sweep_*): one 16-row tile per wave streams best (7168 waves x 64
     // threads for Mixtral GEMM1: 6.7 TB/s vs 6.4 TB/s at two tiles); two tiles only for sub-16-bit
@@ -1117,6 +1126,13 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
         rc = launch_quant_mxfp8_rows(st, x, il.x_ld, h->adt, M, h->H, a->xq, (unsigned char*)a->xqs, true);
         if (rc != LKM_OK) return rc;
     }
+    const int st1 = ceil_div(h->H, 256), st2 = ceil_div(h->I, 256);
+    if (h->mx4) {  // MXFP4 quantisation of the token rows (once per token) into rows of whole 256-k stages + one scale dword pair per stage
+        LKM_REQUIRE((size_t)M * st1 * 128 <= a->xq_n && n_slots * st2 * 128 <= a->aq_n && (size_t)M * st1 * 2 <= a->xqs_n && n_slots * st2 * 2 <= a->aqs_n,
+                    "MXFP4 activation scratch too small");
+        rc = launch_quant_mxfp4_rows(st, x, il.x_ld, h->adt, M, h->H, a->xq, (unsigned char*)a->xqs, true);
+        if (rc != LKM_OK) return rc;
+    }
     if (h->i8a) {  // per-token int8 quantisation of the token rows (once per token): rows of whole units + one fp32 scale per row
         LKM_REQUIRE((size_t)M * kb1 * 128 <= a->xq_n && n_slots * kb2 * 128 <= a->aq_n && (size_t)M <= a->xqs_n && n_slots <= a->aqs_n,
                     "int8 activation scratch too small");
@@ -1196,11 +1212,11 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
     p1.U = h->U1;
     p1.Kreal = h->H;
     p1.n_real = h->I;
-    p1.x = (h->a8 || h->mx8 || h->i8a) ? (const void*)a->xq : x;
-    p1.ldx = h->a8 ? h->H : ((h->mx8 || h->i8a) ? kb1 * 128 : (int)il.x_ld);
+    p1.x = (h->a8 || h->mx8 || h->mx4 || h->i8a) ? (const void*)a->xq : x;
+    p1.ldx = h->a8 ? h->H : ((h->mx8 || h->i8a) ? kb1 * 128 : (h->mx4 ? st1 * 128 : (int)il.x_ld));
     p1.xscale = a->xqs;
-    p1.ld_xscale = h->i8a ? 1 : kb1;
-    p1.round_gemm1 = (h->a8 || h->mx8 || h->i8a) ? 1 : 0;
+    p1.ld_xscale = h->i8a ? 1 : (h->mx4 ? st1 * 2 : kb1);
+    p1.round_gemm1 = (h->a8 || h->mx8 || h->mx4 || h->i8a) ? 1 : 0;
     p1.top_k = K;
     p1.rcp_top_k = 1.0f / (float)K;
     // The gated GEMM1 of the fp8 prefill kernel quantises its own output (the 1 x 128 groups of the W8A8 intermediate:
@@ -1290,15 +1306,19 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
         rc = launch_quant_mxfp8_rows(st, a->act, h->ld_act, h->adt, (int)n_slots, h->I, a->aq, (unsigned char*)a->aqs, true);
         if (rc != LKM_OK) return rc;
     }
+    if (h->mx4) {  // the intermediate (rounded to the activation dtype by GEMM1) through the same quantiser, along I
+        rc = launch_quant_mxfp4_rows(st, a->act, h->ld_act, h->adt, (int)n_slots, h->I, a->aq, (unsigned char*)a->aqs, true);
+        if (rc != LKM_OK) return rc;
+    }
     if (h->i8a) {  // the intermediate (rounded to the activation dtype by GEMM1) through the same quantiser, along I: its amax spans
                    // every weight tile of a row, so this pass cannot live in GEMM1's epilogue
         rc = launch_quant_int8_rows(st, a->act, h->ld_act, h->adt, (int)n_slots, h->I, a->aq, a->aqs, true);
         if (rc != LKM_OK) return rc;
     }
-    p2.x = (h->a8 || h->mx8 || h->i8a) ? (const void*)a->aq : a->act;
-    p2.ldx = (h->mx8 || h->i8a) ? kb2 * 128 : h->ld_act;
+    p2.x = (h->a8 || h->mx8 || h->mx4 || h->i8a) ? (const void*)a->aq : a->act;
+    p2.ldx = (h->mx8 || h->i8a) ? kb2 * 128 : (h->mx4 ? st2 * 128 : h->ld_act);
     p2.xscale = a->aqs;
-    p2.ld_xscale = h->i8a ? 1 : kb2;
+    p2.ld_xscale = h->i8a ? 1 : (h->mx4 ? st2 * 2 : kb2);
     p2.top_k = K;
     p2.rcp_top_k = 1.0f / (float)K;
     p2.counts = a->counts;
@@ -1410,6 +1430,13 @@ static size_t chunk_tokens(const LkmEngine* h, int K) {
         if (h->arena->xqs_n / kb1 < chunk) chunk = h->arena->xqs_n / kb1;
         if (h->arena->aqs_n / ((size_t)K * kb2) < chunk) chunk = h->arena->aqs_n / ((size_t)K * kb2);
     }
+    if (h->mx4) {      // rows of whole 256-k stages: 128 value bytes + two scale dwords per stage
+        const size_t st1 = ceil_div(h->H, 256), st2 = ceil_div(h->I, 256);
+        if (h->arena->xq_n / (st1 * 128) < chunk) chunk = h->arena->xq_n / (st1 * 128);
+        if (h->arena->aq_n / ((size_t)K * st2 * 128) < chunk) chunk = h->arena->aq_n / ((size_t)K * st2 * 128);
+        if (h->arena->xqs_n / (st1 * 2) < chunk) chunk = h->arena->xqs_n / (st1 * 2);
+        if (h->arena->aqs_n / ((size_t)K * st2 * 2) < chunk) chunk = h->arena->aqs_n / ((size_t)K * st2 * 2);
+    }
     if (h->i8a) {      // one fp32 scale per row
         if (h->arena->xqs_n < chunk) chunk = h->arena->xqs_n;
         if (h->arena->aqs_n / (size_t)K < chunk) chunk = h->arena->aqs_n / (size_t)K;
@@ -1451,11 +1478,11 @@ static std::vector<LkmEngine::TunedPlan> tune_candidates(const LkmEngine* h, int
     cands.push_back({0, 0, 0, 0, 0.f, "default"});
     Plan pl;
     pick_cfg(h, M, (size_t)M * K, &pl);
-    if (h->mx8 || h->i8a) {      // one kernel family: the candidates are its other token-tile heights (pick_cfg_mx8 / _i8a ignore "pf" / "pd")
+    if (h->mx8 || h->mx4 || h->i8a) {      // one kernel family: the candidates are its other token-tile heights (pick_cfg_mx8 / _i8a ignore "pf" / "pd")
         for (int t = 32; t <= 256; t *= 2)
             if (t != pl.t1.tiled && (t <= 64 || (size_t)M * K >= (size_t)t)) {
                 LkmEngine::TunedPlan c{0, t, 0, 0, 0.f, ""};
-                snprintf(c.what, sizeof(c.what), "%d-row tiles (%s)", t, h->mx8 ? "gemm_mxa8.h" : "gemm_i8a8.h");
+                snprintf(c.what, sizeof(c.what), "%d-row tiles (%s)", t, h->mx8 ? "gemm_mxa8.h" : (h->mx4 ? "gemm_mxa4.h" : "gemm_i8a8.h"));
                 cands.push_back(c);
             }
         return cands;
@@ -1746,6 +1773,15 @@ extern "C" int lkm_quant_int8_rows(void* stream, const void* x, int32_t x_dtype,
     return launch_quant_int8_rows((hipStream_t)stream, x, ld_x, x_dtype, rows, cols, q, scales, false);
 }
 
+extern "C" int lkm_quant_mxfp4_rows(void* stream, const void* x, int32_t x_dtype, int64_t ld_x, int32_t rows, int32_t cols,
+                                    void* q, uint8_t* scales) {
+    LKM_REQUIRE(x && q && scales, "lkm_quant_mxfp4_rows: null pointer");
+    LKM_REQUIRE(x_dtype == LKM_DT_BF16 || x_dtype == LKM_DT_F16, "lkm_quant_mxfp4_rows: 16-bit activations only");
+    LKM_REQUIRE(rows >= 0 && cols > 0 && cols % 32 == 0 && ld_x >= cols && ld_x % 8 == 0 && ld_x <= 0x7fffffffLL && ((uintptr_t)x & 15) == 0 && ((uintptr_t)q & 3) == 0,
+                "lkm_quant_mxfp4_rows: rows=%d cols=%d ld=%lld (cols a multiple of 32, ld of 8, x 16-byte and q 4-byte aligned)", rows, cols, (long long)ld_x);
+    return launch_quant_mxfp4_rows((hipStream_t)stream, x, ld_x, x_dtype, rows, cols, q, scales, false);
+}
+
 extern "C" int lkm_wna16_expand(void* stream, const void* qweight, const void* scales, const void* zeros, void* out,
                                 int64_t rows, int32_t K, int32_t group, int32_t weight_bits, int32_t out_dtype) {
     LKM_REQUIRE(qweight && scales && out, "lkm_wna16_expand: null pointer");
@@ -1830,7 +1866,7 @@ extern "C" int64_t lkm_weight_bytes(LkmHandle h) { return h ? h->weight_bytes : 
 extern "C" int lkm_describe(LkmHandle h, char* buf, int32_t buf_len) {
     LKM_REQUIRE(h && buf && buf_len > 0, "null argument");
     snprintf(buf, buf_len, "E=%d H=%d I=%d wf=%d%s adt=%d gated=%d T1_half=%d U1=%d T2=%d U2=%d | %s",
-             h->E, h->Hu, h->I, h->wf, h->zp ? " zp=1" : (h->mx8 ? " a8=mxfp8 (gemm_mxa8_kernel)" : (h->i8a ? " a8=int8 (gemm_i8a8_kernel)" : "")), h->adt, (int)h->gated, h->T1_half, h->U1, h->T2, h->U2,
+             h->E, h->Hu, h->I, h->wf, h->zp ? " zp=1" : (h->mx8 ? " a8=mxfp8 (gemm_mxa8_kernel)" : h->mx4 ? " a4=mxfp4 (gemm_mxa4_kernel)" : (h->i8a ? " a8=int8 (gemm_i8a8_kernel)" : "")), h->adt, (int)h->gated, h->T1_half, h->U1, h->T2, h->U2,
              h->last_desc);
     return LKM_OK;
 }
@@ -1993,7 +2029,7 @@ static void expert_slabs(const LkmEngine* h, int expert, ExpertSlabs* s) {
     } else if (h->wf == LKM_W_INT4_B8) {
         sb13 = t13 * 16 * h->spu * 2;
         sb2 = t2 * 16 * h->spu * 2;
-    } else if (h->mx8) {
+    } else if (h->mx8 || h->mx4) {
         sb13 = halves * h->T1_half * (size_t)ceil_div(h->U1, 4) * 256;
         sb2 = (size_t)h->T2 * ceil_div(h->U2, 4) * 256;
     } else if (h->wf == LKM_W_MXFP4 || h->wf == LKM_W_NVFP4) {

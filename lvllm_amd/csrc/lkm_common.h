@@ -233,6 +233,10 @@ __device__ __forceinline__ void store1<f16_out>(f16_out* p, float v) {
 // 0..31 -- the 32 k of ONE scale block per lane, where the weight-only image gives a lane pieces of four blocks -- and the E8M0
 // bytes as [tile][unit / 4][lane] dwords (byte j = unit 4q + j), selected by the instruction's op_sel.
 #define LKM_W_MXFP4_A8 103
+// internal kernel-format code: MXFP4 weights against MXFP4 activations (LkmConfig.fp8_mode = LKM_FP8_MXA4 with LKM_W_MXFP4), both
+// operands of the scaled MFMA fp4 (gemm_mxa4.h).  The weight and scale images are those of LKM_W_MXFP4_A8; the token image is
+// 64 bytes per 128-k unit in rows of whole 256-k stages (dispatch.hip quant_mxfp4_rows_kernel).
+#define LKM_W_MXFP4_A4 105
 // internal kernel-format code: int8 weights against per-token int8 activations (LkmConfig.fp8_mode = LKM_FP8_W8A8 with LKM_W_INT8)
 // on the integer MFMA (gemm_i8a8.h).  The weight image of LKM_W_FP8_A8 byte for byte (signed bytes, zero padding), one fp32
 // scale per weight row as a plain image [expert][tiles * 16].

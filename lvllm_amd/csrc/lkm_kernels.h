@@ -76,6 +76,11 @@ int launch_quant_mxfp8_rows(hipStream_t st, const void* src, long long ld_src, i
 // gemm_i8a8_kernel), scales fp32 [R] = amax / 127
 int launch_quant_int8_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst, float* scales,
                            bool pad);
+// MXFP4 rows (MXFP4 x MXFP4): pad = false -> q [R][K / 2] (two E2M1 per byte, even k low), scales [R][K / 32]; pad = true -> rows
+// padded to whole 256-k stages (q [R][S * 128], scales [R][S * 8] with the eight bytes of a stage ordered [block][unit], pad columns
+// 0 with scale byte 127): the token image of gemm_mxa4_kernel
+int launch_quant_mxfp4_rows(hipStream_t st, const void* src, long long ld_src, int adt, int R, int K, void* dst,
+                            unsigned char* scales, bool pad);
 // int4 fast mode: sums[r][kb] = fp32 sum of the 128 elements of group kb of row r (16-bit rows, row stride ld_src)
 int launch_rowsum128_rows(hipStream_t st, const void* src, int ld_src, int adt, int R, int K, float* sums);
 int launch_combine(hipStream_t st, const void* y, int y_dt, int SK, size_t sk_stride,

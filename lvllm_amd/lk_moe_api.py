@@ -153,7 +153,7 @@ class _MOE:
         wf, adt = self._WEIGHT_FORMAT, self._ACT_DTYPE
         if wf == _clib.W_MXFP4 and int(cfg.fp8_mode) != _clib.FP8_W8A16:
             # the host-resident tier computes on 16-bit activations: it must not stand in for the MXFP8 mode silently
-            raise _clib.LkmError(_clib.E_UNSUPPORTED, "MXFP4 with fp8_mode=1 (MXFP8 activations) has no host-resident (spill) tier; "
+            raise _clib.LkmError(_clib.E_UNSUPPORTED, f"MXFP4 with fp8_mode={int(cfg.fp8_mode)} (MXFP8 / MXFP4 activations) has no host-resident (spill) tier; "
                                  "keep the experts on the GPU or use fp8_mode=0")
         tdt = torch.bfloat16 if adt == _clib.DT_BF16 else torch.float16
         E, H, I = int(cfg.expert_num), int(cfg.hidden_size), int(cfg.intermediate_size)

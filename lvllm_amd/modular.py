@@ -50,7 +50,8 @@ class LkmQuant:
     w1_global_scale: torch.Tensor | None = None
     w2_global_scale: torch.Tensor | None = None
     fp8_mode: int = _clib.FP8_W8A16      # FP8_W8A8: activations quantised on the fly -- fp8: 1x128 (in-tree block-fp8);
-                                         # mxfp4: MXFP8, 1x32 E8M0 blocks (mxfp4_mxfp8_moe_quant_config); int8: per-token int8
+                                         # mxfp4: MXFP8, 1x32 E8M0 blocks (mxfp4_mxfp8_moe_quant_config);
+                                         # FP8_MXA4 (mxfp4 only): MXFP4 activations (mxfp4_moe_quant_config, W4A4); int8: per-token int8
                                          # against fp32 per-channel weight scales (int8_w8a8_moe_quant_config)
     # fmt "wna16": weight-only integers the packed uint4b8 format cannot hold -- zero points and / or 8 bits
     # (fused_moe.py:207-276).  _engine_for hands them to the engine's own zero-point uint4 / uint8 formats where the shape
@@ -110,6 +111,14 @@ class LkmQuant:
                 if getattr(qc, name, None) is not None:
                     raise ValueError(f"MXFP4 x MXFP8 experts with {name} are not supported by the MI355X engine")
             return LkmQuant("mxfp4", qc.w1_scale, qc.w2_scale, 1, 32, fp8_mode=_clib.FP8_W8A8)
+        # MXFP4 weights x dynamically quantised MXFP4 activations (config.py:856-872 mxfp4_moe_quant_config, :442 use_mxfp4_w4a4;
+        # quark's w_mxfp4_a_mxfp4): both operands of the scaled MFMA fp4
+        if getattr(qc, "use_mxfp4_w4a4", False) or (getattr(qc, "quant_dtype", None) == "mxfp4" and
+                                                    getattr(qc, "weight_quant_dtype", None) in ("mxfp4", None)):
+            for name in ("w1_bias", "w2_bias"):
+                if getattr(qc, name, None) is not None:
+                    raise ValueError(f"MXFP4 x MXFP4 experts with {name} are not supported by the MI355X engine")
+            return LkmQuant("mxfp4", qc.w1_scale, qc.w2_scale, 1, 32, fp8_mode=_clib.FP8_MXA4)
         raise ValueError("quantisation scheme of this FusedMoEQuantConfig is not supported by the MI355X engine")
 
 
@@ -198,7 +207,7 @@ class LkmExperts:
         if "fp8" in w and "128" in w:                       # kFp8Static128BlockSym x (None | kFp8Dynamic128Sym)
             return a == "none" or ("fp8" in a and "128" in a)
         if "mxfp4" in w:
-            return a == "none" or "mxfp8" in a              # W4A16, or MXFP8 activations on the scaled MFMA (W4A8)
+            return a == "none" or "mxfp8" in a or "mxfp4" in a    # W4A16, or MXFP8 / MXFP4 activations on the scaled MFMA (W4A8 / W4A4)
         if "nvfp4" in w:
             return a == "none"                              # W4A16
         if _is_i8(w) and _is_i8(a):

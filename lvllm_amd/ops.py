@@ -294,6 +294,19 @@ def quant_int8_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     return q, sc
 
 
+def quant_mxfp4_rows(x: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """x [rows, cols] bf16 / fp16 (cols a multiple of 32, row stride of 8) -> (q uint8 [rows, cols / 2]: two E2M1 per byte, the even
+    column in the low nibble; scales uint8 [rows, cols / 32] E8M0): the MXFP4 quantiser (include/lkm.h lkm_quant_mxfp4_rows) the
+    MXFP4 x MXFP4 engines run on their inputs."""
+    _need_cuda(x)
+    assert x.dim() == 2 and x.stride(1) == 1 and x.dtype in (torch.bfloat16, torch.float16)
+    rows, cols = x.shape
+    q = torch.empty((rows, cols // 2), dtype=torch.uint8, device=x.device)
+    sc = torch.empty((rows, cols // 32), dtype=torch.uint8, device=x.device)
+    _clib.check(_clib.lib().lkm_quant_mxfp4_rows(_stream(x), _ptr(x), _DT[x.dtype], x.stride(0), rows, cols, _ptr(q), _ptr(sc)))
+    return q, sc
+
+
 def wna16_expand(qweight: torch.Tensor, scales: torch.Tensor, zeros: torch.Tensor | None, weight_bits: int,
                  group: int) -> torch.Tensor:
     """Weight-only integer experts -> 16-bit weights T((q - zp) * s), the in-tree operator's dequantisation
@@ -465,7 +478,8 @@ class RoutedExpertsEngine:
         takes them the same way, one byte 0..255 each, both or neither: without them the layer is symmetric uint8b128.
         fp8_mode with fmt "mxfp4": FP8_W8A16 (0) keeps the weight-only path; FP8_W8A8 quantises the hidden states and the
         intermediate to MXFP8 (1 x 32 E8M0 blocks, lkm_quant_mxfp8_rows) and runs both GEMMs on the scaled MFMA
-        (gemm_mxa8_kernel: W4A8, the reference's mxfp4_mxfp8_moe_quant_config).
+        (gemm_mxa8_kernel: W4A8, the reference's mxfp4_mxfp8_moe_quant_config); FP8_MXA4 (4) quantises them to MXFP4
+        (lkm_quant_mxfp4_rows) and both operands of the instruction are fp4 (gemm_mxa4_kernel: W4A4, mxfp4_moe_quant_config).
         fp8_mode with fmt "int8": FP8_W8A16 (0) keeps the weight-only path; FP8_W8A8 is W8A8-int8 (the reference's
         int8_w8a8_moe_quant_config with per_act_token_quant): w13 / w2 are torch.int8 [E, rows, K], the scales fp32 [E, rows]
         (or [E, rows, 1]), one per weight row -- group_n = 1, group_k >= max(hidden, intermediate) -- and there are no zero
