@@ -62,14 +62,22 @@ def ref_layer(a, w13, w2, ids, tw, act, tdt):
     return out
 
 
-def make_layer(rng, E, H, I, gated, tdt, fp8_mode=_clib.FP8_W8A8, K=2, act="silu"):
-    from lvllm_amd.ops import RoutedExpertsEngine
+def make_weights(rng, E, H, I, gated):             # random E2M1 codes, E8M0 scales 2^-9 .. 2^-5 -> (q13, q2, s13, s2)
     n13 = (2 if gated else 1) * I
     q13, q2 = rng.integers(0, 256, (E, n13, H // 2), dtype=np.uint8), rng.integers(0, 256, (E, H, I // 2), dtype=np.uint8)
     s13, s2 = rng.integers(118, 123, (E, n13, H // 32), dtype=np.uint8), rng.integers(118, 123, (E, H, I // 32), dtype=np.uint8)
-    eng = RoutedExpertsEngine(torch.from_numpy(q13), torch.from_numpy(q2), fmt="mxfp4", w13_scale=torch.from_numpy(s13),
-                              w2_scale=torch.from_numpy(s2), group_n=1, group_k=32, top_k=K, act_dtype=tdt, fp8_mode=fp8_mode, **ACTS[act])
-    return eng, deq_w(q13, s13), deq_w(q2, s2)
+    return q13, q2, s13, s2
+
+
+def engine(q13, q2, s13, s2, tdt, K, act="silu", fp8_mode=_clib.FP8_W8A8, **kw):
+    from lvllm_amd.ops import RoutedExpertsEngine
+    return RoutedExpertsEngine(torch.from_numpy(q13), torch.from_numpy(q2), fmt="mxfp4", w13_scale=torch.from_numpy(s13),
+                               w2_scale=torch.from_numpy(s2), group_n=1, group_k=32, top_k=K, act_dtype=tdt, fp8_mode=fp8_mode, **ACTS[act], **kw)
+
+
+def make_layer(rng, E, H, I, gated, tdt, fp8_mode=_clib.FP8_W8A8, K=2, act="silu"):
+    q13, q2, s13, s2 = make_weights(rng, E, H, I, gated)
+    return engine(q13, q2, s13, s2, tdt, K, act, fp8_mode), deq_w(q13, s13), deq_w(q2, s2)
 
 
 def check(out, ref, what=""):                     # the W8A8 tolerance of tests/test_gpu_moe.py, every element
