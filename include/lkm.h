@@ -194,12 +194,39 @@ int lkm_forward_strided(LkmHandle h, void* stream, int32_t num_tokens, int32_t t
  *
  * Replaces torch.ops._moe_C.topk_softmax / topk_sigmoid
  * (vllm/_custom_ops.py:2228-2290 -> csrc/libtorch_stable/moe/topk_softmax_kernels.cu:822-860).
- * logits [M,E] in `logits_dtype` (LKM_DT_*); bias fp32 [E] or NULL; scoring 0=softmax 1=sigmoid.
+ * logits [M,E] in `logits_dtype` (LKM_DT_*); bias fp32 [E] or NULL; scoring: LKM_SCORE_*.
  * Outputs: weights fp32 [M,K], ids int32 [M,K].  DEVICE pointers, async on stream.
+ * lkm_topk_softmax is lkm_topk_route with no hash table and no padding mask.
  */
+#define LKM_SCORE_SOFTMAX 0
+#define LKM_SCORE_SIGMOID 1
+#define LKM_SCORE_SQRTSOFTPLUS 2
 int lkm_topk_softmax(void* stream, const void* logits, int32_t logits_dtype, const float* bias,
                      int32_t M, int32_t E, int32_t K, int32_t scoring, int32_t renormalize,
                      float routed_scaling, float* out_weights, int32_t* out_ids);
+
+/*
+ * The same router with the DeepSeek-V4 arguments of torch.ops._moe_C.topk_hash_softplus_sqrt
+ * (fused_topk_bias_router.py:75-160, csrc/libtorch_stable/moe/topk_softplus_sqrt_kernels.cu); all four optional.
+ *
+ * LKM_SCORE_SQRTSOFTPLUS: score = sqrt(softplus(x)) in fp32, softplus(x) = max(x, 0) + log1p(exp(-|x|)); a NaN or
+ *   infinite score counts as 0.  Experts are CHOSEN by score + bias (bias optional, lowest index among equals); the
+ *   WEIGHT is the unbiased score, divided by sum > 0 ? sum : 1 over the K chosen when `renormalize`, then multiplied
+ *   by routed_scaling.  There is no group-limited sqrtsoftplus router: lkm_grouped_topk and n_group > 0 refuse it.
+ * input_ids int32 [M] + hash_table int32 [vocab_size, K] (both or neither; scoring 2 only): a hash layer.  Row m takes
+ *   ids hash_table[input_ids[m]][0..K) as they stand, no selection, and their unbiased scores as weights (same
+ *   renormalisation; the bias is ignored).  An input id outside [0, vocab_size) gives the whole row ids -1 and
+ *   weights 0; a table entry outside [0, E) gives that slot id -1 and weight 0 and adds nothing to the row's sum.
+ *   Only the K looked-up logits of a row are read.
+ * is_padding uint8 [M] (the storage of a bool tensor), any scoring: a row with a non-zero entry -- a padding row of a
+ *   captured decode batch -- gets ids -1 and weights +0.0; its logits are never read and may hold anything.  The
+ *   engine skips id -1, so lkm_forward_routed_ex spends no expert work on such a row and writes it as zeros.
+ * No allocation, no synchronisation: graph-capturable.
+ */
+int lkm_topk_route(void* stream, const void* logits, int32_t logits_dtype, const float* bias, int32_t M, int32_t E,
+                   int32_t K, int32_t scoring, int32_t renormalize, float routed_scaling, const int32_t* input_ids,
+                   const int32_t* hash_table, int32_t vocab_size, const uint8_t* is_padding, float* out_weights,
+                   int32_t* out_ids);
 
 /*
  * Replaces grouped_topk / torch.ops._moe_C.grouped_topk
@@ -227,6 +254,19 @@ int lkm_forward_routed(LkmHandle h, void* stream, int32_t num_tokens, int32_t to
                        const float* score_bias, int32_t n_group, int32_t topk_group, int32_t scoring,
                        int32_t renormalize, float routed_scaling, int32_t id_offset, float* topk_weights_out,
                        int32_t* topk_ids_out, void* out, int32_t out_dtype);
+/*
+ * lkm_forward_routed with the arguments of lkm_topk_route (input_ids, hash_table, vocab_size, is_padding: all
+ * optional, the same meaning): bit for bit lkm_topk_route (n_group == 0) followed by lkm_forward_strided, fused under
+ * the same conditions as lkm_forward_routed -- a hashed row takes max(8, next power of two >= top_k) lanes, so one
+ * pass of the route + scatter launch covers 64 / that many rows per wavefront.  lkm_forward_routed is this call with
+ * the four arguments NULL / 0.
+ */
+int lkm_forward_routed_ex(LkmHandle h, void* stream, int32_t num_tokens, int32_t top_k, const void* hidden,
+                          int64_t hidden_ld, const void* router_logits, int32_t logits_dtype, int32_t router_experts,
+                          const float* score_bias, int32_t n_group, int32_t topk_group, int32_t scoring,
+                          int32_t renormalize, float routed_scaling, int32_t id_offset, const int32_t* input_ids,
+                          const int32_t* hash_table, int32_t vocab_size, const uint8_t* is_padding,
+                          float* topk_weights_out, int32_t* topk_ids_out, void* out, int32_t out_dtype);
 
 /*
  * Router GEMM + routing in one call: logits = hidden . gate_w^T (+ gate_bias), then the

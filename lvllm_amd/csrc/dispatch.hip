@@ -284,7 +284,7 @@ struct LdsIds {
     }
 };
 
-template <int THREADS, int SLOTS>
+template <int THREADS, int SLOTS, bool EX>
 __global__ __launch_bounds__(THREADS) void route_sort_kernel(
     const RouteArgs ra, int id_off, int E, int32_t* __restrict__ counts,
     int32_t* __restrict__ offsets, int32_t* __restrict__ sorted_slot,
@@ -295,8 +295,8 @@ __global__ __launch_bounds__(THREADS) void route_sort_kernel(
     __shared__ int32_t s_ids[kRouteSortSlots];
     __shared__ float s_ch[WAVES][SLOTS * 64];    // group-limited routing only
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group);
-    route_rows<SLOTS>(ra, wv * rpw, WAVES * rpw, lane, s_ch[wv], s_ids);
+    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group, EX && ra.hash_table != nullptr);
+    route_rows<SLOTS, EX>(ra, wv * rpw, WAVES * rpw, lane, s_ch[wv], s_ids);
     __syncthreads();
     // the sort runs on as few wavefronts as the problem needs (one for <= 64 slots: its barriers are then free); the
     // others are done -- a barrier counts the wavefronts that have not ended
@@ -569,9 +569,10 @@ static void launch_sort_t(hipStream_t st, const SlotIds ids, int n_slots, int E,
 }
 
 // router + sort in one launch: worth it while the ONE workgroup routes the batch in at most two passes of its 16
-// wavefronts (a row's routing is a ~2 us dependency chain; the stand-alone router spreads rows over the chip)
-bool launch_route_sort_ok(int M, int K, int E_router, int n_group, int E_local) {
-    const int rpw = route_rows_per_wave(E_router, K, n_group);
+// wavefronts (a row's routing is a ~2 us dependency chain; the stand-alone router spreads rows over the chip); a wavefront
+// takes four rows at E <= 16 and 64 / P hashed rows (routing_dev.h route_rows_per_wave)
+bool launch_route_sort_ok(int M, int K, int E_router, int n_group, int E_local, bool hash) {
+    const int rpw = route_rows_per_wave(E_router, K, n_group, hash);
     return (long long)M * K <= kRouteSortSlots && K <= 64 && E_router <= 256 && E_local <= 256 && M <= 2 * 16 * rpw;
 }
 template <int THREADS, int SLOTS>
@@ -581,20 +582,24 @@ static void launch_route_sort_t(hipStream_t st, const RouteArgs& ra, int id_offs
                                 int xcd_cap, size_t tiles) {
     constexpr int W = THREADS / 64;
     const size_t lds = sizeof(int32_t) * ((size_t)3 * E + 4 * W + (size_t)W * E + 16 + tiles);
-    hipLaunchKernelGGL((route_sort_kernel<THREADS, SLOTS>), dim3(1), dim3(THREADS), lds, st, ra, id_offset, E, counts,
-                       offsets, sorted_slot, pos_of_slot, active, meta, tile_rows, tile_min, tile_e, tile_r0, xcd_cap);
+    if (route_is_ex(ra))       // (scoring 2, a hash table or a padding mask: routing_dev.h)
+        hipLaunchKernelGGL((route_sort_kernel<THREADS, SLOTS, true>), dim3(1), dim3(THREADS), lds, st, ra, id_offset, E, counts,
+                           offsets, sorted_slot, pos_of_slot, active, meta, tile_rows, tile_min, tile_e, tile_r0, xcd_cap);
+    else
+        hipLaunchKernelGGL((route_sort_kernel<THREADS, SLOTS, false>), dim3(1), dim3(THREADS), lds, st, ra, id_offset, E, counts,
+                           offsets, sorted_slot, pos_of_slot, active, meta, tile_rows, tile_min, tile_e, tile_r0, xcd_cap);
 }
 int launch_route_sort(hipStream_t st, const RouteArgs& ra, int id_offset, int E, int32_t* counts, int32_t* offsets,
                       int32_t* sorted_slot, int32_t* pos_of_slot, int32_t* active, int32_t* meta, int tile_rows,
                       int tile_min, int32_t* tile_e, int32_t* tile_r0, int xcd_cap) {
     const int n_slots = ra.M * ra.K;
-    LKM_REQUIRE(launch_route_sort_ok(ra.M, ra.K, ra.E, ra.n_group, E), "route+sort: M=%d K=%d E=%d out of range", ra.M, ra.K, ra.E);
+    LKM_REQUIRE(launch_route_sort_ok(ra.M, ra.K, ra.E, ra.n_group, E, ra.hash_table != nullptr), "route+sort: M=%d K=%d E=%d out of range", ra.M, ra.K, ra.E);
     const size_t tiles = xcd_cap > 0 ? (size_t)((tile_rows & 0xffff) > 0 ? n_slots / (tile_rows & 0xffff) : 0) + E : 0;
-    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group);
+    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group, ra.hash_table != nullptr);
     const bool small = ceil_div(ra.M, rpw) <= 4;        // 4 wavefronts route it in one pass: cheaper barriers in the sort
 #define LKM_RS(T, S) launch_route_sort_t<T, S>(st, ra, id_offset, E, counts, offsets, sorted_slot, pos_of_slot, active, \
                                                meta, tile_rows, tile_min, tile_e, tile_r0, xcd_cap, tiles)
-    switch (route_slots(ra.E)) {
+    switch (ra.hash_table ? 1 : route_slots(ra.E)) {      // (a hashed row holds no scores in register slots)
     case 1: if (small) LKM_RS(256, 1); else LKM_RS(1024, 1); break;
     case 2: if (small) LKM_RS(256, 2); else LKM_RS(1024, 2); break;
     default: if (small) LKM_RS(256, 4); else LKM_RS(1024, 4); break;

@@ -740,14 +740,24 @@ __global__ __launch_bounds__(512) void gemm1_act_kernel(GemmParams p) {
                     if (ra.n_group > 0)
                         grouped_topk_row<S>(ra.src, ra.bias, rrow, ra.E, ra.K, ra.n_group, ra.topk_group, ra.scoring,
                                             ra.renorm, ra.rsf, ln, sh_ch, w, id);
+                    else if (ra.scoring == 2)
+                        topk_row<S, 64, true>(ra.src, ra.bias, rrow, ra.E, ra.K, 2, ra.renorm, ra.rsf, ln, w, id);
                     else
                         topk_row<S, 64>(ra.src, ra.bias, rrow, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, ln, w, id);
                 };
-                switch (route_slots(ra.E)) {
-                case 1: go(SlotsC<1>{}); break;
-                case 2: go(SlotsC<2>{}); break;
-                case 4: go(SlotsC<4>{}); break;
-                default: go(SlotsC<8>{}); break;
+                // a padding token keeps (-1, +0) and its logits unread; a hashed token is one lane group of this wavefront
+                // (hash_row: the other groups repeat it, lanes k < K sit in group 0)
+                if (ra.is_padding && ra.is_padding[rrow]) {
+                } else if (ra.hash_table) {
+                    const int P = route_hash_lanes(ra.K);
+                    hash_row(ra, rrow, true, ln & (P - 1), P, w, id);
+                } else {
+                    switch (route_slots(ra.E)) {
+                    case 1: go(SlotsC<1>{}); break;
+                    case 2: go(SlotsC<2>{}); break;
+                    case 4: go(SlotsC<4>{}); break;
+                    default: go(SlotsC<8>{}); break;
+                    }
                 }
                 if (ln < ra.K) {
                     sh_id[ln] = id;

@@ -1170,7 +1170,7 @@ static int run_chunk(LkmEngine* h, hipStream_t st, int M, int K, const void* x, 
     const bool want_xcd = tile_rows && max_tiles <= 4096 && (h->t_xcd > 0 || pl.xcd1 || pl.xcd2);
     const int xcd_cap = want_xcd ? 2 * ((max_tiles + 7) / 8) + 1 : 0;
     if (!direct && il.route) {
-        LKM_REQUIRE(launch_route_sort_ok(M, K, il.route->E, il.route->n_group, h->E), "forward_routed: step planned off both fused paths");
+        LKM_REQUIRE(launch_route_sort_ok(M, K, il.route->E, il.route->n_group, h->E, il.route->hash_table != nullptr), "forward_routed: step planned off both fused paths");
         rc = launch_route_sort(st, *il.route, il.id_off, h->E, a->counts, a->offsets, a->sorted_slot, a->pos_of_slot,
                                a->active, a->meta, tile_rows_sort, tile_min_sort, a->tile_e, a->tile_r0, xcd_cap);
         if (rc != LKM_OK) return rc;
@@ -1652,17 +1652,20 @@ extern "C" int lkm_forward_strided(LkmHandle h, void* stream, int32_t num_tokens
     return run_device(h, (hipStream_t)stream, num_tokens, top_k, hidden, topk_ids, topk_weights, out, out_dtype, &il);
 }
 
-extern "C" int lkm_forward_routed(LkmHandle h, void* stream, int32_t num_tokens, int32_t top_k, const void* hidden,
-                                  int64_t hidden_ld, const void* router_logits, int32_t logits_dtype,
-                                  int32_t router_experts, const float* score_bias, int32_t n_group,
-                                  int32_t topk_group, int32_t scoring, int32_t renormalize, float routed_scaling,
-                                  int32_t id_offset, float* topk_weights_out, int32_t* topk_ids_out, void* out,
-                                  int32_t out_dtype) {
+extern "C" int lkm_forward_routed_ex(LkmHandle h, void* stream, int32_t num_tokens, int32_t top_k, const void* hidden,
+                                     int64_t hidden_ld, const void* router_logits, int32_t logits_dtype,
+                                     int32_t router_experts, const float* score_bias, int32_t n_group,
+                                     int32_t topk_group, int32_t scoring, int32_t renormalize, float routed_scaling,
+                                     int32_t id_offset, const int32_t* input_ids, const int32_t* hash_table,
+                                     int32_t vocab_size, const uint8_t* is_padding, float* topk_weights_out,
+                                     int32_t* topk_ids_out, void* out, int32_t out_dtype) {
     LKM_REQUIRE(h, "null engine handle");
     LKM_REQUIRE(out_dtype == LKM_DT_F32 || out_dtype == h->adt, "forward_routed: out_dtype must be fp32 or the activation dtype");
     LKM_REQUIRE(id_offset >= 0, "forward_routed: id_offset must be >= 0");
     const int M = num_tokens, K = top_k, E = router_experts;
     LKM_REQUIRE(M >= 0 && E > 0 && K > 0 && K <= E && K <= 64, "forward_routed: bad shape M=%d E=%d K=%d", M, E, K);
+    const int rce = check_route_ex("forward_routed", scoring, n_group, input_ids, hash_table, vocab_size);
+    if (rce != LKM_OK) return rce;
     if (M == 0) return LKM_OK;
     LKM_REQUIRE(router_logits && topk_weights_out && topk_ids_out, "forward_routed: null device pointer");
     // one chunk, batched path: the router rides in the sort launch; otherwise the two calls it stands for
@@ -1671,7 +1674,7 @@ extern "C" int lkm_forward_routed(LkmHandle h, void* stream, int32_t num_tokens,
     // route all M rows against one chunk's scratch)
     size_t eff_chunk = chunk_tokens(h, K);
     if (h->Hu != h->H && h->pad_tokens < eff_chunk) eff_chunk = h->pad_tokens;
-    bool fused = M > 1 && launch_route_sort_ok(M, K, E, n_group, h->E) && h->t_fuse >= 0 && eff_chunk >= (size_t)M;
+    bool fused = M > 1 && launch_route_sort_ok(M, K, E, n_group, h->E, hash_table != nullptr) && h->t_fuse >= 0 && eff_chunk >= (size_t)M;
     if (M <= direct_max_tokens(h) && h->t_fuse >= 0 && eff_chunk >= (size_t)M) {
         // one to four tokens: the direct path (two launches) routes inside GEMM1 -- when the plan takes that path
         Plan pl;
@@ -1679,18 +1682,8 @@ extern "C" int lkm_forward_routed(LkmHandle h, void* stream, int32_t num_tokens,
         if (direct_plan(h, M, K, pl)) fused = true;
     }
     InLayout il{hidden_ld, K, K, id_offset};
-    if (!fused) {
-        int rc = n_group > 0 ? lkm_grouped_topk(stream, router_logits, logits_dtype, score_bias, M, E, K, n_group,
-                                                topk_group, scoring, renormalize, routed_scaling, topk_weights_out,
-                                                topk_ids_out)
-                             : lkm_topk_softmax(stream, router_logits, logits_dtype, score_bias, M, E, K, scoring,
-                                                renormalize, routed_scaling, topk_weights_out, topk_ids_out);
-        if (rc != LKM_OK) return rc;
-        return run_device(h, (hipStream_t)stream, M, K, hidden, topk_ids_out, topk_weights_out, out, out_dtype, &il);
-    }
     LKM_REQUIRE(E <= kMaxSlots * 64, "forward_routed: router_experts=%d > %d unsupported", E, kMaxSlots * 64);
     LKM_REQUIRE(logits_dtype >= LKM_DT_F32 && logits_dtype <= LKM_DT_F16, "forward_routed: bad logits dtype");
-    LKM_REQUIRE(scoring == 0 || scoring == 1, "forward_routed: scoring must be 0 (softmax) or 1 (sigmoid)");
     if (n_group > 0) {
         LKM_REQUIRE(n_group <= 64 && E % n_group == 0, "forward_routed: n_group=%d must divide E=%d and be <= 64", n_group, E);
         LKM_REQUIRE(topk_group > 0 && topk_group <= n_group, "forward_routed: bad topk_group=%d", topk_group);
@@ -1709,8 +1702,28 @@ extern "C" int lkm_forward_routed(LkmHandle h, void* stream, int32_t num_tokens,
     ra.rsf = routed_scaling;
     ra.out_w = topk_weights_out;
     ra.out_ids = topk_ids_out;
-    il.route = &ra;
+    ra.input_ids = input_ids;
+    ra.hash_table = hash_table;
+    ra.vocab_size = vocab_size;
+    ra.is_padding = is_padding;
+    if (!fused) {
+        const int rc = launch_route((hipStream_t)stream, ra);
+        if (rc != LKM_OK) return rc;
+    } else {
+        il.route = &ra;
+    }
     return run_device(h, (hipStream_t)stream, M, K, hidden, topk_ids_out, topk_weights_out, out, out_dtype, &il);
+}
+
+extern "C" int lkm_forward_routed(LkmHandle h, void* stream, int32_t num_tokens, int32_t top_k, const void* hidden,
+                                  int64_t hidden_ld, const void* router_logits, int32_t logits_dtype,
+                                  int32_t router_experts, const float* score_bias, int32_t n_group,
+                                  int32_t topk_group, int32_t scoring, int32_t renormalize, float routed_scaling,
+                                  int32_t id_offset, float* topk_weights_out, int32_t* topk_ids_out, void* out,
+                                  int32_t out_dtype) {
+    return lkm_forward_routed_ex(h, stream, num_tokens, top_k, hidden, hidden_ld, router_logits, logits_dtype, router_experts,
+                                 score_bias, n_group, topk_group, scoring, renormalize, routed_scaling, id_offset, nullptr,
+                                 nullptr, 0, nullptr, topk_weights_out, topk_ids_out, out, out_dtype);
 }
 
 extern "C" int lkm_prefill_host(LkmHandle h, int32_t num_tokens, int32_t top_k,

@@ -39,6 +39,12 @@ int launch_repack_s_fp4(hipStream_t st, const void* src, void* dst, const Repack
 // MXFP4 x MXFP8 (LKM_W_MXFP4_A8): E8M0 scales [E][N][K/32] -> [E][tile][ceil(U / 4)][lane] dwords (gemm_mxa8.h)
 int launch_repack_s_mxa8(hipStream_t st, const void* src, void* dst, const RepackDims& d);
 
+// ---- routing.hip: the checks every routing entry point makes on scoring / hash arguments (include/lkm.h lkm_topk_route)
+int check_route_ex(const char* who, int scoring, int n_group, const int32_t* input_ids, const int32_t* hash_table,
+                   int vocab_size);
+// the stand-alone router launch on a checked argument block
+int launch_route(hipStream_t st, const RouteArgs& ra);
+
 // ---- dispatch.hip
 // Work list of the round-3 fp8 x fp8 prefill kernel: for each of the two GEMMs (rg1 / rg2 row groups per token tile),
 // every (token tile, row group) item as {expert, offsets[e] + first row, rows, row group}, ordered inside each part of the
@@ -55,7 +61,7 @@ int launch_sort(hipStream_t st, const int32_t* ids, int top_k, int ids_ld, int i
                 int32_t* hist, size_t hist_cap, int xcd_cap = 0);
 // router + sort in one launch for decode batches (RouteArgs: routing_dev.h); same outputs as the router kernel
 // followed by launch_sort
-bool launch_route_sort_ok(int M, int K, int E_router, int n_group, int E_local);
+bool launch_route_sort_ok(int M, int K, int E_router, int n_group, int E_local, bool hash);
 int launch_route_sort(hipStream_t st, const RouteArgs& ra, int id_offset, int E, int32_t* counts, int32_t* offsets,
                       int32_t* sorted_slot, int32_t* pos_of_slot, int32_t* active, int32_t* meta, int tile_rows,
                       int tile_min, int32_t* tile_e, int32_t* tile_r0, int xcd_cap);

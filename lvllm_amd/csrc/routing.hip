@@ -1,8 +1,9 @@
-// routing.hip -- router kernels for gfx950 (wave64): fused softmax/sigmoid top-k, group-limited
-// top-k, global->local expert id map.
+// routing.hip -- router kernels for gfx950 (wave64): fused softmax / sigmoid / sqrtsoftplus top-k (hash-table ids and
+// padding rows: routing_dev.h), group-limited top-k, global->local expert id map.
 //
 // What they compute follows the reference (paths relative to the reference tree):
 //   topk_softmax   csrc/libtorch_stable/moe/topk_softmax_kernels.cu:408-592
+//   sqrtsoftplus   csrc/libtorch_stable/moe/topk_softplus_sqrt_kernels.cu:77-122, 326-420
 //   grouped_topk   vllm/model_executor/layers/fused_moe/router/grouped_topk_router.py:112-161
 //   id map         vllm/model_executor/layers/fused_moe/routed_experts.py:1332-1342
 // How: one 64-lane wavefront per token row, expert e lives in lane e%64 (register slot e/64),
@@ -16,24 +17,28 @@
 namespace lkm {
 
 // One launch routes M rows: 4 wavefronts per workgroup, one row per wavefront (four when E <= 16: a row then takes
-// 16 lanes), register slots by expert count (routing_dev.h).
-template <int SLOTS>
+// 16 lanes; 64 / P hashed rows of P lanes each), register slots by expert count (routing_dev.h).
+template <int SLOTS, bool EX>
 __global__ __launch_bounds__(256) void route_kernel(const RouteArgs ra) {
     __shared__ float lds_ch[4][SLOTS * 64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group);
-    route_rows<SLOTS>(ra, (blockIdx.x * 4 + wv) * rpw, gridDim.x * 4 * rpw, lane, lds_ch[wv], nullptr);
+    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group, EX && ra.hash_table != nullptr);
+    route_rows<SLOTS, EX>(ra, (blockIdx.x * 4 + wv) * rpw, gridDim.x * 4 * rpw, lane, lds_ch[wv], nullptr);
 }
 
-static int launch_route(hipStream_t st, const RouteArgs& ra) {
-    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group);
+int launch_route(hipStream_t st, const RouteArgs& ra) {
+    const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group, ra.hash_table != nullptr);
     const dim3 grid(ceil_div(ra.M, 4 * rpw)), block(256);
-    switch (route_slots(ra.E)) {
-    case 1: hipLaunchKernelGGL(route_kernel<1>, grid, block, 0, st, ra); break;
-    case 2: hipLaunchKernelGGL(route_kernel<2>, grid, block, 0, st, ra); break;
-    case 4: hipLaunchKernelGGL(route_kernel<4>, grid, block, 0, st, ra); break;
-    default: hipLaunchKernelGGL(route_kernel<8>, grid, block, 0, st, ra); break;
+    switch (ra.hash_table ? 1 : route_slots(ra.E)) {      // (a hashed row holds no scores in register slots)
+#define LKM_ROUTE(S)                                                                                   \
+    if (route_is_ex(ra)) hipLaunchKernelGGL((route_kernel<S, true>), grid, block, 0, st, ra);          \
+    else hipLaunchKernelGGL((route_kernel<S, false>), grid, block, 0, st, ra)
+    case 1: LKM_ROUTE(1); break;
+    case 2: LKM_ROUTE(2); break;
+    case 4: LKM_ROUTE(4); break;
+    default: LKM_ROUTE(8); break;
     }
+#undef LKM_ROUTE
     LKM_HIP_CHECK(hipGetLastError());
     return LKM_OK;
 }
@@ -47,22 +52,42 @@ __global__ void map_ids_kernel(const int32_t* __restrict__ ids, int64_t n,
     out[i] = id < 0 ? -1 : map[c];
 }
 
+// the checks every entry point makes on the DeepSeek-V4 arguments (include/lkm.h lkm_topk_route)
+int check_route_ex(const char* who, int scoring, int n_group, const int32_t* input_ids, const int32_t* hash_table,
+                   int vocab_size) {
+    LKM_REQUIRE(scoring >= LKM_SCORE_SOFTMAX && scoring <= LKM_SCORE_SQRTSOFTPLUS, "%s: scoring must be 0 (softmax), 1 (sigmoid) or 2 (sqrtsoftplus)", who);
+    LKM_REQUIRE(scoring != LKM_SCORE_SQRTSOFTPLUS || n_group <= 0, "%s: sqrtsoftplus has no group-limited router", who);
+    LKM_REQUIRE((input_ids != nullptr) == (hash_table != nullptr), "%s: input_ids and hash_table come together", who);
+    LKM_REQUIRE(!hash_table || (scoring == LKM_SCORE_SQRTSOFTPLUS && vocab_size > 0), "%s: a hash table needs scoring 2 (sqrtsoftplus) and vocab_size > 0", who);
+    return LKM_OK;
+}
+
 }  // namespace lkm
 
 using namespace lkm;
+
+extern "C" int lkm_topk_route(void* stream, const void* logits, int32_t logits_dtype, const float* bias, int32_t M,
+                              int32_t E, int32_t K, int32_t scoring, int32_t renormalize, float routed_scaling,
+                              const int32_t* input_ids, const int32_t* hash_table, int32_t vocab_size,
+                              const uint8_t* is_padding, float* out_weights, int32_t* out_ids) {
+    LKM_REQUIRE(M >= 0 && E > 0 && K > 0 && K <= E && K <= 64, "topk_route: bad shape M=%d E=%d K=%d", M, E, K);
+    LKM_REQUIRE(E <= kMaxSlots * 64, "topk_route: E=%d > %d unsupported", E, kMaxSlots * 64);
+    LKM_REQUIRE(logits_dtype >= LKM_DT_F32 && logits_dtype <= LKM_DT_F16, "topk_route: bad dtype");
+    const int rc = check_route_ex("topk_route", scoring, 0, input_ids, hash_table, vocab_size);
+    if (rc != LKM_OK) return rc;
+    if (M == 0) return LKM_OK;
+    const LogitSrc src{logits, logits_dtype, 1, 0, nullptr, LKM_DT_F32, nullptr};
+    const RouteArgs ra{src, bias, M, E, K, 0, 0, scoring, renormalize, routed_scaling, out_weights, out_ids,
+                       input_ids, hash_table, vocab_size, is_padding};
+    return launch_route((hipStream_t)stream, ra);
+}
 
 extern "C" int lkm_topk_softmax(void* stream, const void* logits, int32_t logits_dtype,
                                 const float* bias, int32_t M, int32_t E, int32_t K,
                                 int32_t scoring, int32_t renormalize, float routed_scaling,
                                 float* out_weights, int32_t* out_ids) {
-    LKM_REQUIRE(M >= 0 && E > 0 && K > 0 && K <= E && K <= 64, "topk_softmax: bad shape M=%d E=%d K=%d", M, E, K);
-    LKM_REQUIRE(E <= kMaxSlots * 64, "topk_softmax: E=%d > %d unsupported", E, kMaxSlots * 64);
-    LKM_REQUIRE(logits_dtype >= LKM_DT_F32 && logits_dtype <= LKM_DT_F16, "topk_softmax: bad dtype");
-    LKM_REQUIRE(scoring == 0 || scoring == 1, "topk_softmax: scoring must be 0 (softmax) or 1 (sigmoid)");
-    if (M == 0) return LKM_OK;
-    const LogitSrc src{logits, logits_dtype, 1, 0, nullptr, LKM_DT_F32, nullptr};
-    const RouteArgs ra{src, bias, M, E, K, 0, 0, scoring, renormalize, routed_scaling, out_weights, out_ids};
-    return launch_route((hipStream_t)stream, ra);
+    return lkm_topk_route(stream, logits, logits_dtype, bias, M, E, K, scoring, renormalize, routed_scaling, nullptr,
+                          nullptr, 0, nullptr, out_weights, out_ids);
 }
 
 extern "C" int lkm_grouped_topk(void* stream, const void* logits, int32_t logits_dtype,
@@ -79,7 +104,8 @@ extern "C" int lkm_grouped_topk(void* stream, const void* logits, int32_t logits
     LKM_REQUIRE(scoring == 0 || scoring == 1, "grouped_topk: scoring must be 0 or 1");
     if (M == 0) return LKM_OK;
     const LogitSrc src{logits, logits_dtype, 1, 0, nullptr, LKM_DT_F32, nullptr};
-    const RouteArgs ra{src, bias, M, E, K, n_group, topk_group, scoring, renormalize, routed_scaling, out_weights, out_ids};
+    const RouteArgs ra{src, bias, M, E, K, n_group, topk_group, scoring, renormalize, routed_scaling, out_weights, out_ids,
+                       nullptr, nullptr, 0, nullptr};
     return launch_route((hipStream_t)stream, ra);
 }
 
@@ -282,7 +308,8 @@ extern "C" int lkm_router_gemm_topk(void* stream, const void* x, int32_t x_dtype
     const bool w32 = w_dtype == LKM_DT_F32;
     LKM_REQUIRE(H % (w32 ? 16 : 32) == 0, "router: hidden_size=%d must be a multiple of %d", H, w32 ? 16 : 32);
     LKM_REQUIRE(logits_dtype == LKM_DT_F32 || logits_dtype == x_dtype, "router: logits_dtype must be fp32 or the activation dtype");
-    LKM_REQUIRE(scoring == 0 || scoring == 1, "router: scoring must be 0 (softmax) or 1 (sigmoid)");
+    const int rce = check_route_ex("router", scoring, n_group, nullptr, nullptr, 0);
+    if (rce != LKM_OK) return rce;
     if (n_group > 0) {
         LKM_REQUIRE(n_group <= 64 && E % n_group == 0, "router: n_group=%d must divide E=%d and be <= 64", n_group, E);
         LKM_REQUIRE(topk_group > 0 && topk_group <= n_group, "router: bad topk_group=%d", topk_group);
@@ -349,7 +376,7 @@ extern "C" int lkm_router_gemm_topk(void* stream, const void* x, int32_t x_dtype
     }
     const LogitSrc src{part, LKM_DT_F32, KS, (long long)M * E, gate_bias, logits_dtype, logits_out};
     const RouteArgs ra{src, score_bias, M, E, K, n_group > 0 ? n_group : 0, topk_group, scoring, renormalize, routed_scaling,
-                       out_weights, out_ids};
+                       out_weights, out_ids, nullptr, nullptr, 0, nullptr};
     return launch_route(st, ra);
 }
 

@@ -72,8 +72,9 @@ __device__ __forceinline__ float wave_max64(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 
-// scores for one row, in registers: sc[s] = score of expert s*LPR+sub (0 for e >= E)
-template <int SLOTS, int LPR>
+// scores for one row, in registers: sc[s] = score of expert s*LPR+sub (0 for e >= E).  SQ: the scoring IS sqrtsoftplus
+// (a template argument, so the softmax / sigmoid instantiations are the code they were before scoring 2 existed)
+template <int SLOTS, int LPR, bool SQ = false>
 __device__ __forceinline__ void row_scores(const LogitSrc& src, int row, int E, int sub,
                                            int scoring, float (&sc)[SLOTS]) {
 #pragma clang fp contract(off)
@@ -83,7 +84,13 @@ __device__ __forceinline__ void row_scores(const LogitSrc& src, int row, int E, 
         int e = s * LPR + sub;
         v[s] = (e < E) ? src.load(row, E, e) : -__builtin_inff();
     }
-    if (scoring == 0) {
+    if constexpr (SQ) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            int e = s * LPR + sub;
+            sc[s] = (e < E) ? lkm_sqrtsoftplus(v[s]) : 0.0f;
+        }
+    } else if (scoring == 0) {
         float mx = v[0];
 #pragma unroll
         for (int s = 1; s < SLOTS; ++s) mx = fmaxf(mx, v[s]);
@@ -160,14 +167,15 @@ __device__ __forceinline__ void select_max64(float (&ch)[SLOTS], const float (&s
     }
 }
 
-// Plain top-k of one row (softmax / sigmoid scores, optional selection bias).  Lane sub == k of the row's group
+// Plain top-k of one row (softmax / sigmoid / sqrtsoftplus scores, optional selection bias: the bias chooses, the
+// weight is the unbiased score).  Lane sub == k of the row's group
 // (k < K <= LPR) returns selection k in (w, id): the weight is final (renormalised, scaled).
-template <int SLOTS, int LPR>
+template <int SLOTS, int LPR, bool SQ = false>
 __device__ __forceinline__ void topk_row(const LogitSrc& src, const float* __restrict__ bias, int row, int E, int K,
                                          int scoring, int renorm, float rsf, int sub, float& w, int& id) {
 #pragma clang fp contract(off)
     float sc[SLOTS], ch[SLOTS];
-    row_scores<SLOTS, LPR>(src, row, E, sub, scoring, sc);
+    row_scores<SLOTS, LPR, SQ>(src, row, E, sub, scoring, sc);
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
         int e = s * LPR + sub;
@@ -288,7 +296,8 @@ __device__ __forceinline__ void grouped_topk_row(const LogitSrc& src, const floa
 }
 
 // What the router computes, as one argument block; route_rows() is the body shared by the stand-alone router kernels
-// (routing.hip) and the fused router + scatter launch (dispatch.hip).
+// (routing.hip) and the fused router + scatter launch (dispatch.hip); the in-GEMM1 router (gemm_skinny.h) calls the row
+// functions on its one token.
 struct RouteArgs {
     LogitSrc src;
     const float* bias;      // selection bias [E] or null
@@ -298,41 +307,127 @@ struct RouteArgs {
     float rsf;
     float* out_w;           // [M][K] fp32
     int32_t* out_ids;       // [M][K] int32 (global ids)
+    // hash layers (scoring 2 only): ids = hash_table[input_ids[row]][0..K), no selection; both or neither
+    const int32_t* input_ids;    // [M]
+    const int32_t* hash_table;   // [vocab_size][K]
+    int vocab_size;
+    const uint8_t* is_padding;   // [M] or null: a non-zero row gets ids -1, weights +0 and its logits are never read
 };
 
 // register slots a row needs (1, 2, 4 or 8) and rows per wavefront for a router shape
 __host__ __device__ inline int route_slots(int E) { return E <= 64 ? 1 : (E <= 128 ? 2 : (E <= 256 ? 4 : 8)); }
-__host__ __device__ inline int route_rows_per_wave(int E, int K, int n_group) { return (n_group <= 0 && E <= 16 && K <= 16) ? 4 : 1; }
+// lanes of a hashed row: max(8, next power of two >= K)
+__host__ __device__ inline int route_hash_lanes(int K) {
+    int p = 8;
+    while (p < K) p <<= 1;
+    return p;
+}
+__host__ __device__ inline int route_rows_per_wave(int E, int K, int n_group, bool hash) {
+    if (hash) return 64 / route_hash_lanes(K);
+    return (n_group <= 0 && E <= 16 && K <= 16) ? 4 : 1;
+}
 
-// Routes rows  first_row + i * row_step  (i = 0, 1, ...; this wavefront's rows of a pass) -- every wavefront of the
-// launch calls it with the same trip count.  lds_ch: SLOTS*64 floats per wavefront (group-limited routing only);
-// s_ids: optional LDS copy of the ids [M*K].
-template <int SLOTS>
+// A hashed row: no selection rounds and K logits, not E.  The row takes P = route_hash_lanes(K) lanes; lane sub = k < K
+// looks its expert up, loads that ONE logit and scores it; the sum for the renormalisation is an xor butterfly over
+// the P lanes (steps P/2 .. 1: lanes k >= K, bad entries and idle rows add +0, which is exact, so the bits do not
+// depend on P or on the neighbours in the wavefront).  Every lane of the wavefront calls it (shuffles); `live` = this
+// lane's row exists and is not padding.  A token id outside [0, vocab) voids the row, a table entry outside [0, E)
+// voids the slot (id -1, weight 0, nothing added to the sum); both are checked before the load they would index.
+__device__ __forceinline__ void hash_row(const RouteArgs& ra, int row, bool live, int sub, int P, float& w, int& id) {
+#pragma clang fp contract(off)
+    float sc = 0.0f;
+    id = -1;
+    if (live && sub < ra.K) {
+        const int tok = ra.input_ids[row];
+        if (tok >= 0 && tok < ra.vocab_size) {
+            const int e = ra.hash_table[(size_t)tok * ra.K + sub];
+            if (e >= 0 && e < ra.E) {
+                id = e;
+                sc = lkm_sqrtsoftplus(ra.src.load(row, ra.E, e));
+                if (__builtin_isnan(sc) || __builtin_isinf(sc)) sc = 0.0f;
+            }
+        }
+    }
+    float sum = sc;
+#pragma unroll
+    for (int m = 32; m > 0; m >>= 1)
+        if (m < P) sum = sum + __shfl_xor(sum, m, 64);      // (P is wave-uniform)
+    float scale = ra.rsf;
+    if (ra.renorm) scale /= (sum > 0.0f ? sum : 1.0f);
+    w = id >= 0 ? sc * scale : 0.0f;
+}
+
+// Routes rows  first_row + i * row_step  (i = 0, 1, ...; this wavefront's rows of a pass).  lds_ch: SLOTS*64 floats per
+// wavefront (group-limited routing only); s_ids: optional LDS copy of the ids [M*K].  A row takes 64 / rows-per-wave lanes.
+// EX = false: softmax / sigmoid scores, no hash table, no padding mask -- the router as it was.  EX = true
+// (route_is_ex): any scoring; lane groups without a live row (past M, or padding) write -1 / +0 (nothing past M) and
+// load nothing: in a wavefront with no live row the whole pass is skipped (wave-uniform), otherwise such a group
+// repeats the work of the wavefront's first live row and drops the result.
+__host__ __device__ inline bool route_is_ex(const RouteArgs& ra) { return ra.scoring == 2 || ra.hash_table || ra.is_padding; }
+
+template <int SLOTS, bool EX>
 __device__ __forceinline__ void route_rows(const RouteArgs& ra, int first_row, int row_step, int lane, float* lds_ch,
                                            int32_t* s_ids) {
-    const bool four = route_rows_per_wave(ra.E, ra.K, ra.n_group) == 4;
-    for (int base = first_row; base < ra.M; base += row_step) {
-        float w;
-        int id, row, sub;
-        if (ra.n_group > 0) {
-            row = base;
-            sub = lane;
-            grouped_topk_row<SLOTS>(ra.src, ra.bias, row, ra.E, ra.K, ra.n_group, ra.topk_group, ra.scoring, ra.renorm,
-                                    ra.rsf, lane, lds_ch, w, id);
-        } else if (SLOTS == 1 && four) {
-            row = base + (lane >> 4);
-            sub = lane & 15;
-            const int rowc = row < ra.M ? row : ra.M - 1;     // a lane group past the last row repeats it, writes nothing
-            topk_row<1, 16>(ra.src, ra.bias, rowc, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, sub, w, id);
-        } else {
-            row = base;
-            sub = lane;
-            topk_row<SLOTS, 64>(ra.src, ra.bias, row, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, sub, w, id);
+    if constexpr (!EX) {
+        const bool four = route_rows_per_wave(ra.E, ra.K, ra.n_group, false) == 4;
+        for (int base = first_row; base < ra.M; base += row_step) {
+            float w;
+            int id, row, sub;
+            if (ra.n_group > 0) {
+                row = base;
+                sub = lane;
+                grouped_topk_row<SLOTS>(ra.src, ra.bias, row, ra.E, ra.K, ra.n_group, ra.topk_group, ra.scoring, ra.renorm,
+                                        ra.rsf, lane, lds_ch, w, id);
+            } else if (SLOTS == 1 && four) {
+                row = base + (lane >> 4);
+                sub = lane & 15;
+                const int rowc = row < ra.M ? row : ra.M - 1;     // a lane group past the last row repeats it, writes nothing
+                topk_row<1, 16>(ra.src, ra.bias, rowc, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, sub, w, id);
+            } else {
+                row = base;
+                sub = lane;
+                topk_row<SLOTS, 64>(ra.src, ra.bias, row, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, sub, w, id);
+            }
+            if (row < ra.M && sub < ra.K) {
+                ra.out_w[(size_t)row * ra.K + sub] = w;
+                ra.out_ids[(size_t)row * ra.K + sub] = id;
+                if (s_ids) s_ids[row * ra.K + sub] = id;
+            }
         }
-        if (row < ra.M && sub < ra.K) {
-            ra.out_w[(size_t)row * ra.K + sub] = w;
-            ra.out_ids[(size_t)row * ra.K + sub] = id;
-            if (s_ids) s_ids[row * ra.K + sub] = id;
+    } else {
+        const bool hash = ra.hash_table != nullptr, sq = ra.scoring == 2;
+        const int rpw = route_rows_per_wave(ra.E, ra.K, ra.n_group, hash);
+        const int lpr = 64 / rpw, sh = __builtin_ctz(lpr), sub = lane & (lpr - 1);
+        for (int base = first_row; base < ra.M; base += row_step) {
+            const int row = base + (lane >> sh);
+            const bool live = row < ra.M && !(ra.is_padding && ra.is_padding[row]);
+            const unsigned long long lv = __ballot(live);
+            float w = 0.0f;
+            int id = -1;
+            if (lv != 0ull) {
+                if (hash) {
+                    hash_row(ra, row, live, sub, lpr, w, id);
+                } else if (ra.n_group > 0) {
+                    grouped_topk_row<SLOTS>(ra.src, ra.bias, base, ra.E, ra.K, ra.n_group, ra.topk_group, ra.scoring, ra.renorm,
+                                            ra.rsf, lane, lds_ch, w, id);
+                } else if (SLOTS == 1 && rpw == 4) {
+                    const int rowc = live ? row : base + ((__ffsll((long long)lv) - 1) >> sh);      // the first live lane's row
+                    if (sq) topk_row<1, 16, true>(ra.src, ra.bias, rowc, ra.E, ra.K, 2, ra.renorm, ra.rsf, sub, w, id);
+                    else topk_row<1, 16>(ra.src, ra.bias, rowc, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, sub, w, id);
+                } else {
+                    if (sq) topk_row<SLOTS, 64, true>(ra.src, ra.bias, base, ra.E, ra.K, 2, ra.renorm, ra.rsf, sub, w, id);
+                    else topk_row<SLOTS, 64>(ra.src, ra.bias, base, ra.E, ra.K, ra.scoring, ra.renorm, ra.rsf, sub, w, id);
+                }
+                if (!live) {
+                    w = 0.0f;
+                    id = -1;
+                }
+            }
+            if (row < ra.M && sub < ra.K) {
+                ra.out_w[(size_t)row * ra.K + sub] = w;
+                ra.out_ids[(size_t)row * ra.K + sub] = id;
+                if (s_ids) s_ids[row * ra.K + sub] = id;
+            }
         }
     }
 }

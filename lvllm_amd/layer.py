@@ -41,6 +41,15 @@ class RoutingConfig:
     e_score_correction_bias: torch.Tensor | None = None
     routed_scaling_factor: float = 1.0
     apply_routed_scaling_in_router: bool = False     # grouped_topk_router.py:156-160 scales the weights itself
+    hash_indices_table: torch.Tensor | None = None   # DeepSeek-V4 hash layers: [vocab, top_k] token id -> expert ids
+
+    def __post_init__(self):
+        if self.hash_indices_table is not None:
+            if self.scoring_func != "sqrtsoftplus":
+                raise ValueError("a hash table needs scoring_func='sqrtsoftplus'")
+            self.hash_indices_table = self.hash_indices_table.to(torch.int32).contiguous()   # once, not per step
+        if self.scoring_func == "sqrtsoftplus" and self.use_grouped_topk:
+            raise ValueError("sqrtsoftplus has no group-limited router")
 
 
 class RoutedExpertsLayer:
@@ -84,24 +93,42 @@ class RoutedExpertsLayer:
         self._decode_out: torch.Tensor | None = None          # the shared fp32 buffer of the cpu_decode contract
 
     # ---- a1 / a2 (+ gate projection, f2)
-    def select_experts(self, hidden_states: torch.Tensor, router_logits: torch.Tensor | None):
+    def _route_kw(self, input_ids, is_padding) -> dict:
+        """the DeepSeek-V4 router keywords of the ops -- only those that are set, so an operator namespace that
+        predates them keeps working"""
+        kw = {}
+        if self.routing.hash_indices_table is not None:
+            if input_ids is None:
+                raise ValueError("a hash layer routes by token id: pass input_ids")
+            kw["input_tokens"] = input_ids
+            kw["hash_indices_table"] = self.routing.hash_indices_table
+        if is_padding is not None:
+            kw["is_padding"] = is_padding
+        return kw
+
+    def select_experts(self, hidden_states: torch.Tensor, router_logits: torch.Tensor | None, input_ids=None,
+                       is_padding=None):
         r = self.routing
         scale = r.routed_scaling_factor if r.apply_routed_scaling_in_router else 1.0
+        kw = self._route_kw(input_ids, is_padding)
         if self.gate_weight is not None:
             return self.ops.router_topk(hidden_states, self.gate_weight, r.top_k, r.renormalize,
                                         scoring_func=r.scoring_func,
                                         num_expert_group=r.num_expert_group if r.use_grouped_topk else 0,
                                         topk_group=r.topk_group if r.use_grouped_topk else 0,
-                                        routed_scaling_factor=scale, e_score_correction_bias=r.e_score_correction_bias)
+                                        routed_scaling_factor=scale, e_score_correction_bias=r.e_score_correction_bias,
+                                        **kw)
         if router_logits is None:
             raise ValueError("router_logits are required when the layer has no gate_weight")
         if router_logits.size(0) != hidden_states.size(0):
             raise ValueError("Number of tokens mismatch")
         if r.use_grouped_topk:
+            if kw:
+                raise ValueError("group-limited routing takes no hash table and no padding mask")
             return self.ops.grouped_topk(hidden_states, router_logits, r.top_k, r.renormalize, r.num_expert_group,
                                          r.topk_group, r.scoring_func, scale, r.e_score_correction_bias)
         return self.ops.topk_softmax(router_logits, r.top_k, r.renormalize, r.e_score_correction_bias, r.scoring_func,
-                                     scale)
+                                     scale, **kw)
 
     def _decode_buffer(self, hidden_states: torch.Tensor) -> torch.Tensor:
         buf = self._decode_out
@@ -112,10 +139,13 @@ class RoutedExpertsLayer:
         return buf
 
     # ---- the whole step
-    def forward(self, hidden_states: torch.Tensor, router_logits: torch.Tensor | None = None) -> torch.Tensor:
+    def forward(self, hidden_states: torch.Tensor, router_logits: torch.Tensor | None = None, input_ids=None,
+                is_padding=None) -> torch.Tensor:
         """[M, H] activations (+ [M, E] logits unless the layer owns the gate) -> [M, H] in the activation dtype:
         the routed (+ folded shared) experts' output of THIS rank, before the TP/EP reduction (with
-        `expert_parallel`: the complete output for this rank's tokens)."""
+        `expert_parallel`: the complete output for this rank's tokens).  input_ids [M]: the token ids a hash layer
+        (RoutingConfig.hash_indices_table) routes by; is_padding bool [M]: padding rows of a captured batch, which
+        are routed nowhere."""
         M = hidden_states.size(0)
         if M == 0:
             return torch.empty_like(hidden_states)
@@ -132,14 +162,15 @@ class RoutedExpertsLayer:
                 num_expert_group=r.num_expert_group if r.use_grouped_topk else 0,
                 topk_group=r.topk_group if r.use_grouped_topk else 0,
                 routed_scaling_factor=r.routed_scaling_factor if r.apply_routed_scaling_in_router else 1.0,
-                e_score_correction_bias=r.e_score_correction_bias, out=buf[:M])
+                e_score_correction_bias=r.e_score_correction_bias, out=buf[:M],
+                **self._route_kw(input_ids, is_padding))
             if self.check_nan_in_output:
                 torch.nan_to_num(out, nan=0.0, out=out)
             out = out.to(hidden_states.dtype)
             if r.routed_scaling_factor != 1.0 and not r.apply_routed_scaling_in_router:
                 out *= r.routed_scaling_factor
             return out
-        topk_weights, topk_ids = self.select_experts(hidden_states, router_logits)
+        topk_weights, topk_ids = self.select_experts(hidden_states, router_logits, input_ids, is_padding)
         if self.eplb_state is not None:                       # BaseRouter._apply_eplb_mapping, base_router.py:204-223
             s = self.eplb_state
             topk_ids = self.ops.eplb_map_to_physical_and_record(

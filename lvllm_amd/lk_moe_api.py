@@ -262,13 +262,18 @@ class _MOE:
                        logits_ptr: int, logits_dtype: int, router_experts: int, score_bias_ptr: int,
                        n_group: int, topk_group: int, scoring: int, renormalize: bool, routed_scaling: float,
                        id_offset: int, topk_weights_ptr: int, topk_ids_ptr: int, out_ptr: int,
-                       out_dtype: int) -> None:
-        _clib.check(self._lib.lkm_forward_routed(self._h, _vp(stream), num_tokens, top_k, _vp(hidden_ptr),
-                                                 int(hidden_ld), _vp(logits_ptr), int(logits_dtype),
-                                                 int(router_experts), _vp(score_bias_ptr), int(n_group),
-                                                 int(topk_group), int(scoring), int(bool(renormalize)),
-                                                 float(routed_scaling), int(id_offset), _vp(topk_weights_ptr),
-                                                 _vp(topk_ids_ptr), _vp(out_ptr), int(out_dtype)))
+                       out_dtype: int, *, input_ids_ptr: int = 0, hash_table_ptr: int = 0, vocab_size: int = 0,
+                       is_padding_ptr: int = 0) -> None:
+        """include/lkm.h lkm_forward_routed_ex; the keywords are the DeepSeek-V4 router's optional arguments (int32
+        token ids [M], int32 hash table [vocab_size, top_k], uint8 padding mask [M])."""
+        _clib.check(self._lib.lkm_forward_routed_ex(self._h, _vp(stream), num_tokens, top_k, _vp(hidden_ptr),
+                                                    int(hidden_ld), _vp(logits_ptr), int(logits_dtype),
+                                                    int(router_experts), _vp(score_bias_ptr), int(n_group),
+                                                    int(topk_group), int(scoring), int(bool(renormalize)),
+                                                    float(routed_scaling), int(id_offset), _vp(input_ids_ptr),
+                                                    _vp(hash_table_ptr), int(vocab_size), _vp(is_padding_ptr),
+                                                    _vp(topk_weights_ptr), _vp(topk_ids_ptr), _vp(out_ptr),
+                                                    int(out_dtype)))
 
     # ---- measurement / introspection (extensions) --------------------------------------
     def set_profiling(self, enable: bool) -> None:

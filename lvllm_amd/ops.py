@@ -23,7 +23,7 @@ from .lk_moe_api import (MOE_BF16, MOE_FP16, MOE_FP8, MOE_FP8_FP16, MOE_MXFP4, M
                          MOE_NVFP4, MOE_NVFP4_FP16, MOE_WNA16, MOE_WNA16_FP16, MOEConfigV2)
 
 _DT = {torch.float32: _clib.DT_F32, torch.bfloat16: _clib.DT_BF16, torch.float16: _clib.DT_F16}
-_SCORING = {"softmax": 0, "sigmoid": 1}
+_SCORING = {"softmax": 0, "sigmoid": 1, "sqrtsoftplus": 2}
 
 
 def _stream(t: torch.Tensor) -> C.c_void_p:
@@ -40,13 +40,43 @@ def _need_cuda(*ts: torch.Tensor) -> None:
             raise ValueError("lvllm_amd ops run on the GPU only (got a CPU tensor); there is no CPU path")
 
 
+def _route_ex(M: int, topk: int, scoring_func: str, input_tokens, hash_indices_table, is_padding):
+    """The DeepSeek-V4 router arguments (include/lkm.h lkm_topk_route) as what the C call takes:
+    -> (input ids int32 [M] | None, hash table int32 [vocab, topk] | None, vocab, padding mask uint8 [M] | None)."""
+    if (input_tokens is None) != (hash_indices_table is None):
+        raise ValueError("input_tokens and hash_indices_table come together")
+    tok = tab = pad = None
+    vocab = 0
+    if hash_indices_table is not None:
+        if scoring_func != "sqrtsoftplus":
+            raise ValueError("a hash table needs scoring_func='sqrtsoftplus'")
+        _need_cuda(input_tokens, hash_indices_table)
+        tok = input_tokens.reshape(-1).to(torch.int32).contiguous()
+        tab = hash_indices_table.to(torch.int32).contiguous()
+        if tok.numel() != M or tab.dim() != 2 or tab.size(1) != topk:
+            raise ValueError(f"input_tokens must be [{M}] and hash_indices_table [vocab, {topk}]")
+        vocab = tab.size(0)
+    if is_padding is not None:
+        _need_cuda(is_padding)
+        pad = is_padding.reshape(-1).contiguous()
+        pad = pad.view(torch.uint8) if pad.dtype == torch.bool else (pad != 0).view(torch.uint8)
+        if pad.numel() != M:
+            raise ValueError(f"is_padding must be [{M}]")
+    return tok, tab, vocab, pad
+
+
 def topk_softmax(gating_output: torch.Tensor, topk: int, renormalize: bool,
                  e_score_correction_bias: torch.Tensor | None = None,
-                 scoring_func: str = "softmax", routed_scaling_factor: float = 1.0):
-    """-> (topk_weights fp32 [M,K], topk_ids int32 [M,K])"""
-    _need_cuda(gating_output, e_score_correction_bias)
+                 scoring_func: str = "softmax", routed_scaling_factor: float = 1.0, *,
+                 input_tokens: torch.Tensor | None = None, hash_indices_table: torch.Tensor | None = None,
+                 is_padding: torch.Tensor | None = None):
+    """-> (topk_weights fp32 [M,K], topk_ids int32 [M,K]).  scoring_func "sqrtsoftplus" is the DeepSeek-V4 router
+    (fused_topk_bias_router.py:75-160): the bias chooses, the weights are the unbiased scores; with input_tokens [M]
+    and hash_indices_table [vocab, K] the ids are looked up, not selected; rows set in is_padding (bool [M]) get
+    ids -1 and weights 0 and their logits are not read."""
     if scoring_func not in _SCORING:
         raise ValueError(f"Unsupported scoring function: {scoring_func}")
+    _need_cuda(gating_output, e_score_correction_bias)
     if gating_output.dtype not in _DT:
         raise ValueError(f"unsupported gating dtype {gating_output.dtype}")
     g = gating_output.contiguous()
@@ -56,9 +86,10 @@ def topk_softmax(gating_output: torch.Tensor, topk: int, renormalize: bool,
         bias = e_score_correction_bias.to(torch.float32).contiguous()
     w = torch.empty((M, topk), dtype=torch.float32, device=g.device)
     ids = torch.empty((M, topk), dtype=torch.int32, device=g.device)
-    _clib.check(_clib.lib().lkm_topk_softmax(_stream(g), _ptr(g), _DT[g.dtype], _ptr(bias), M, E, topk,
-                                             _SCORING[scoring_func], int(renormalize),
-                                             float(routed_scaling_factor), _ptr(w), _ptr(ids)))
+    tok, tab, vocab, pad = _route_ex(M, topk, scoring_func, input_tokens, hash_indices_table, is_padding)
+    _clib.check(_clib.lib().lkm_topk_route(_stream(g), _ptr(g), _DT[g.dtype], _ptr(bias), M, E, topk,
+                                           _SCORING[scoring_func], int(renormalize), float(routed_scaling_factor),
+                                           _ptr(tok), _ptr(tab), vocab, _ptr(pad), _ptr(w), _ptr(ids)))
     return w, ids
 
 
@@ -78,11 +109,14 @@ def fused_topk(hidden_states: torch.Tensor, gating_output: torch.Tensor, topk: i
 
 
 def fused_topk_bias(hidden_states: torch.Tensor, gating_output: torch.Tensor,
-                    e_score_correction_bias: torch.Tensor, topk: int, renormalize: bool,
-                    scoring_func: str = "softmax", routed_scaling_factor: float = 1.0):
+                    e_score_correction_bias: torch.Tensor | None, topk: int, renormalize: bool,
+                    scoring_func: str = "softmax", routed_scaling_factor: float = 1.0, *,
+                    input_tokens: torch.Tensor | None = None, hash_indices_table: torch.Tensor | None = None,
+                    is_padding: torch.Tensor | None = None):
     assert hidden_states.size(0) == gating_output.size(0), "Number of tokens mismatch"
     return topk_softmax(gating_output, topk, renormalize, e_score_correction_bias, scoring_func,
-                        routed_scaling_factor)
+                        routed_scaling_factor, input_tokens=input_tokens, hash_indices_table=hash_indices_table,
+                        is_padding=is_padding)
 
 
 def grouped_topk(hidden_states: torch.Tensor, gating_output: torch.Tensor, topk: int,
@@ -91,9 +125,11 @@ def grouped_topk(hidden_states: torch.Tensor, gating_output: torch.Tensor, topk:
                  e_score_correction_bias: torch.Tensor | None = None):
     """grouped_topk_router.py:80-161 -> (topk_weights fp32, topk_ids int32)."""
     assert hidden_states.size(0) == gating_output.size(0), "Number of tokens mismatch"
-    _need_cuda(gating_output, e_score_correction_bias)
     if scoring_func not in _SCORING:
         raise ValueError(f"Unsupported scoring function: {scoring_func}")
+    if scoring_func == "sqrtsoftplus":
+        raise ValueError("sqrtsoftplus has no group-limited router")
+    _need_cuda(gating_output, e_score_correction_bias)
     g = gating_output.contiguous()
     M, E = g.shape
     bias = None
@@ -115,14 +151,22 @@ def router_topk(hidden_states: torch.Tensor, gate_weight: torch.Tensor, topk: in
                 gate_bias: torch.Tensor | None = None, scoring_func: str = "softmax",
                 num_expert_group: int = 0, topk_group: int = 0, routed_scaling_factor: float = 1.0,
                 e_score_correction_bias: torch.Tensor | None = None,
-                logits_dtype: torch.dtype = torch.float32, return_logits: bool = False):
+                logits_dtype: torch.dtype = torch.float32, return_logits: bool = False,
+                input_tokens: torch.Tensor | None = None, hash_indices_table: torch.Tensor | None = None,
+                is_padding: torch.Tensor | None = None):
     """Gate projection + routing in one call: what moe_runner.py:903-908 + fused_topk /
     grouped_topk do in two operators.  gate_weight [E,H] in the activation dtype or fp32 (GateLinear
     force_fp32_compute); logits_dtype fp32 (router GEMMs with fp32 output) or the activation dtype
-    (F.linear in the gate's dtype).  -> (topk_weights fp32, topk_ids int32[, router_logits fp32])."""
-    _need_cuda(hidden_states, gate_weight, gate_bias, e_score_correction_bias)
+    (F.linear in the gate's dtype).  -> (topk_weights fp32, topk_ids int32[, router_logits fp32]).
+    A hash table or a padding mask is not served behind the gate projection: route the logits with topk_softmax."""
     if scoring_func not in _SCORING:
         raise ValueError(f"Unsupported scoring function: {scoring_func}")
+    if input_tokens is not None or hash_indices_table is not None or is_padding is not None:
+        raise ValueError("router_topk takes no hash table and no padding mask together with gate_weight: "
+                         "compute the logits and call topk_softmax")
+    if scoring_func == "sqrtsoftplus" and num_expert_group > 0:
+        raise ValueError("sqrtsoftplus has no group-limited router")
+    _need_cuda(hidden_states, gate_weight, gate_bias, e_score_correction_bias)
     x, gw = hidden_states.contiguous(), gate_weight.contiguous()
     M, H = x.shape
     E = gw.shape[0]
@@ -599,14 +643,18 @@ class RoutedExpertsEngine:
                        scoring_func: str = "softmax", num_expert_group: int = 0, topk_group: int = 0,
                        routed_scaling_factor: float = 1.0, e_score_correction_bias: torch.Tensor | None = None,
                        out: torch.Tensor | None = None, out_dtype: torch.dtype = torch.float32,
-                       id_offset: int = 0):
-        """Routing + experts in one call (include/lkm.h lkm_forward_routed): topk_softmax / grouped_topk on
+                       id_offset: int = 0, input_tokens: torch.Tensor | None = None,
+                       hash_indices_table: torch.Tensor | None = None, is_padding: torch.Tensor | None = None):
+        """Routing + experts in one call (include/lkm.h lkm_forward_routed_ex): topk_softmax / grouped_topk on
         `router_logits` [M, E_router], then the operator on the result; for decode batches the router and the
         scatter metadata are one launch.  Bit-identical to topk_softmax()/grouped_topk() followed by
-        forward_rows().  -> (out [M,H], topk_weights fp32 [M,K], topk_ids int32 [M,K])"""
-        _need_cuda(hidden, router_logits, e_score_correction_bias)
+        forward_rows(); input_tokens / hash_indices_table / is_padding as in topk_softmax (a padding row comes out
+        as zeros).  -> (out [M,H], topk_weights fp32 [M,K], topk_ids int32 [M,K])"""
         if scoring_func not in _SCORING:
             raise ValueError(f"Unsupported scoring function: {scoring_func}")
+        if scoring_func == "sqrtsoftplus" and num_expert_group > 0:
+            raise ValueError("sqrtsoftplus has no group-limited router")
+        _need_cuda(hidden, router_logits, e_score_correction_bias)
         if router_logits.dtype not in _DT:
             raise ValueError(f"unsupported gating dtype {router_logits.dtype}")
         assert hidden.dtype == self.act_dtype and hidden.dim() == 2 and (hidden.size(1) == 1 or hidden.stride(1) == 1)
@@ -623,11 +671,15 @@ class RoutedExpertsEngine:
         assert out.is_contiguous() and out.dtype in (torch.float32, self.act_dtype)
         if M == 0:
             return out, w, ids
+        tok, tab, vocab, pad = _route_ex(M, topk, scoring_func, input_tokens, hash_indices_table, is_padding)
         self.engine.forward_routed(torch.cuda.current_stream(hidden.device).cuda_stream, M, topk, hidden.data_ptr(),
                                    hidden.stride(0) if M > 1 else max(hidden.stride(0), self.H), g.data_ptr(),
                                    _DT[g.dtype], E, 0 if bias is None else bias.data_ptr(), int(num_expert_group), int(topk_group),
                                    _SCORING[scoring_func], renormalize, float(routed_scaling_factor), int(id_offset),
-                                   w.data_ptr(), ids.data_ptr(), out.data_ptr(), _DT[out.dtype])
+                                   w.data_ptr(), ids.data_ptr(), out.data_ptr(), _DT[out.dtype],
+                                   input_ids_ptr=0 if tok is None else tok.data_ptr(),
+                                   hash_table_ptr=0 if tab is None else tab.data_ptr(), vocab_size=vocab,
+                                   is_padding_ptr=0 if pad is None else pad.data_ptr())
         return out, w, ids
 
     def prefill_host(self, hidden: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor) -> torch.Tensor:
